@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
 """ORB front-end throughput on MI355X: features/ms and frames/s of the extractor hot path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
-Started without WORLD_SIZE and with N > 1, the script re-executes itself under `torch.distributed.run` with one rank per
+A plain run sets up, warms up, times exactly K steps once and prints the headline line (`value`, `ms_per_step` of those K steps).
+--full adds everything else this docstring describes: the median of --repeats timed loops, the oracle check of the last step, the
+per-kernel roofline, the exchange legs and the N = 1 extras.  --dump-outputs DIR writes the last timed step's features as .npy files.
+
+Started without WORLD_SIZE and with N > 1, the script starts itself under `torch.distributed.run` with one rank per
 visible GPU (min(N, visible); the line reports the world size RCCL actually saw).  Started by a launcher (RANK / LOCAL_RANK /
 WORLD_SIZE set) it is one rank of that job.
 
@@ -12,12 +16,12 @@ A "step" is one pass of the hot path (pyramid -> FAST cells -> quadtree -> orien
 (S-EuRoC-640: 640x480, 8 levels, 1000 features) replayed in batches; the steps rotate through several DISTINCT batches (more
 input than the 256 MB Infinity Cache holds); every rank replays its own camera stream (seed + 1000*rank), i.e. weak scaling,
 and for N > 1 the per-step feature blocks are all-gathered over RCCL asynchronously (batch-replay mode).
-After the timed region frames of the last step are compared with the CPU oracle ("verified_frames"); a mismatch fails the run.
-At N = 1 the same line also carries: the end-to-end latency of ORBextractor::operator() through the C++ adapter (host buffers),
+With --full, after the timed region frames of the last step are compared with the CPU oracle ("verified_frames"); a mismatch fails
+the run.  With --full at N = 1 the same line also carries: the end-to-end latency of ORBextractor::operator() through the C++ adapter (host buffers),
 the streamed front-end (operator() + BoW transform + the two per-frame guided searches as one loop, next to the same loop on the
 reference-compiled CPU code), a secondary measurement of BASELINE config 4 (1024x1024, 2000 features) with its own roofline, and the
 CPU baseline (the reference's own src/ORBextractor.cc compiled where it lies + this repository's port).
---streams 8 selects SURVEY 8(e)'s curve (the same 8 camera streams on G GPUs); N > 1 lines report the all-gather's device time.
+--streams 8 selects SURVEY 8(e)'s curve (the same 8 camera streams on G GPUs); N > 1 --full lines report the all-gather's device time.
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -347,6 +351,31 @@ def verify_block(eng, block_index, host_frames, frame_ids, nfeatures, lap, varia
                 raise SystemExit(f"bench.py: frame {f} of the last timed step differs from the CPU oracle "
                                  f"({len(kps)} vs {len(okps)} keypoints) — the measured path is WRONG, no number reported")
     return len(frame_ids)
+
+
+def dump_outputs(out_dir, block, layout, limit_bytes=64 * 10 ** 6):
+    """One finished step's features as a caller of the replay receives them (unpack_block), written to out_dir/<name>.npy: per frame its index in
+    the batch, monoIndex and keypoint count (float64), then every keypoint's seven orbx_keypoint fields and its 32 descriptor bytes (float32, exact).
+    Frames that would pass `limit_bytes` are left out by a fixed-seed draw, so that two builds given the same arguments write the same frames."""
+    from orb_slam3_modified_amd.replay import unpack_block
+    res = unpack_block(block, layout)
+    keep, total = [], 0
+    for f in np.random.default_rng(0).permutation(len(res)):
+        size = 3 * 8 + len(res[f][1]) * (7 + 32) * 4
+        if total + size > limit_bytes:
+            break
+        keep.append(int(f))
+        total += size
+    keep.sort()
+    kps = np.concatenate([res[f][1] for f in keep])
+    out = {"frame_index": np.array(keep, np.float64),
+           "mono_index": np.array([res[f][0] for f in keep], np.float64),
+           "n_keypoints": np.array([len(res[f][1]) for f in keep], np.float64),
+           "keypoints": np.stack([kps[name].astype(np.float32) for name in kps.dtype.names], axis=1),
+           "descriptors": np.concatenate([res[f][2] for f in keep]).astype(np.float32)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def fast_cells_per_frame(rows, cols, nlevels=8, sf=1.2):
@@ -735,8 +764,14 @@ def main():
     ap.add_argument("--cpu-budget", type=float, default=24.0, help="seconds of CPU work for the cpu_baseline leg")
     ap.add_argument("--lanes", type=int, default=int(os.environ.get("ORBX_LANES", "2")),
                     help="extractor contexts per GPU, each on its own free-running stream over 1/lanes of the batch")
-    ap.add_argument("--repeats", type=int, default=9, help="the --steps-long timed loop is run this many times (each bracketed by barrier + synchronize): "
-                                                          "ms_per_step / value are the MEDIAN repeat's, min / max / spread are reported beside them")
+    ap.add_argument("--repeats", type=int, default=None, help="the --steps-long timed loop is run this many times (each bracketed by barrier + synchronize): "
+                                                           "ms_per_step / value are the MEDIAN repeat's, min / max / spread are reported beside them "
+                                                           "(default 1; 9 with --full)")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline: repeats, the oracle check, the roofline, "
+                                                        "the exchange legs, the fixed-8-stream record and the N = 1 extras (each --no-* option drops one)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the features the last timed step computed (rank 0) to DIR/<name>.npy, float32 / float64, at most 64 MB (a seeded "
+                         "sample of the frames when the batch holds more)")
     ap.add_argument("--profile", default="opencv>=4.5.1", help="which CPU path the output must equal (orbx_set_cpu_profile; INTEGRATION.md section 6): "
                                                               "opencv>=4.5.1 | opencv-4.4 | opencv-4.4-sse | opencv-4.4-avx512 | opencv-4.4-scalar | opencv-3.2")
     ap.add_argument("--fma-build", type=int, default=0, help="bit 0: the reference built with -march=native on an FMA machine; bit 1: OpenCV's AVX2 fastAtan2")
@@ -746,6 +781,8 @@ def main():
                          "path of this script is exercised on a one-GPU box (tests/test_bench_contract.py); never a configuration to quote")
     ap.add_argument("--share-gpu", action="store_true", help="testing only: every rank uses cuda:0 (RCCL refuses a shared device: needs --control-backend gloo)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 9 if args.full else 1
     args.repeats = max(1, args.repeats) | 1      # odd: the median is a measured repeat
     if args.batch is None:
         args.batch = 256   # per camera stream; SURVEY 8(e)'s B = 64 leaves a GPU two 32-frame lanes at G = 8 (measured: -20 %)
@@ -759,10 +796,10 @@ def main():
     requested = max(1, args.gpus)
     if "WORLD_SIZE" not in os.environ and requested > 1:
         n = min(requested, torch.cuda.device_count())
-        if n > 1:   # become the launcher: one rank per GPU over RCCL
+        if n > 1:   # start the launcher as a child (one rank per GPU over RCCL); this process has touched the GPU and only waits
             s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-            os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr",
-                                      "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+            return subprocess.call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr",
+                                    "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
     rank = int(os.environ.get("RANK", "0"))
     local_rank = 0 if args.share_gpu else int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -848,10 +885,12 @@ def main():
     order = sorted(range(args.repeats), key=lambda r: dts[r])
     rmed = order[args.repeats // 2]
     dt, last = dts[rmed], lasts[-1]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng.block_host(last), eng.layout)
     # the exchange: device time of one step's collective (HIP events on the gather stream), and the same timed loop with / without it,
     # alternating repeats -> how much of the collective the next step's kernels hide
     exchange = None
-    if eng.gather:
+    if eng.gather and args.full:
         exchange = {"collective": f"ncclAllGather({args.gather}) called by liborbx (orbx_replay_step), one per step, async on its own stream, double-buffered",
                     "transport": eng.transport, "bytes_per_rank_per_step": int(eng.send_bytes), "bytes_received_per_rank_per_step": int(eng.send_bytes * (world - 1))}
         exchange.update(exchange_legs(eng, args.steps, max(3, args.repeats // 2 + 1), sync_all, reduce_max))
@@ -881,17 +920,20 @@ def main():
     value = total_feats / (dt * 1e3)
 
     lane_edges = sorted({0, B - 1, B // 2 - 1, B // 2} | {f for (f0, f1) in eng.lane_ranges for f in (f0, f1 - 1)} | {B // 3})
-    verified = 0 if args.no_verify else verify_block(eng, last, host_frames[last_set * B:(last_set + 1) * B], lane_edges, args.nfeatures, (0, 1000), args.variant)
+    verified = 0
+    if args.full and not args.no_verify:
+        verified = verify_block(eng, last, host_frames[last_set * B:(last_set + 1) * B], lane_edges, args.nfeatures, (0, 1000), args.variant)
     vt = torch.tensor([verified], dtype=torch.int64, device=cdev)
     if world > 1:
         dist.all_reduce(vt, op=dist.ReduceOp.SUM)
 
     strong = None
-    if args.streams == 0 and not args.no_fixed_streams:   # every rank takes part
+    if args.full and args.streams == 0 and not args.no_fixed_streams:   # every rank takes part
         strong = fixed_streams_leg(args, ex, dev, rank, world, cdev, sync_all, reduce_max, want_gather and exchange_error is None)
 
-    if rank == 0:
-        dom, nkp, fused, roof = kernel_roofline(ex, eng, frame_sets[0], B, H, W, counts, world, args.steps, dt)
+    nkp = float(counts[:, 0].mean())
+    if rank == 0 and args.full:
+        dom, _, fused, roof = kernel_roofline(ex, eng, frame_sets[0], B, H, W, counts, world, args.steps, dt)
         # HBM traffic and issue-side counters of the dominant kernel come from committed rocprofv3 --pmc passes (tools/pmc_traffic.py,
         # tools/pmc_sq.py): they are only reported when the files are stamped with the hash of the kernel sources this run was built from
         from orb_slam3_modified_amd.build import kernels_hash
@@ -932,12 +974,13 @@ def main():
                     roof["issue_limits_pmc"] = {"source": f"profiles/pmc_sq.json is STALE (kernel sources {st.get('kernels_hash')}, this build {khash}): not reported"}
             except Exception:
                 pass
-        step_ms = dt / args.steps * 1e3
         rr = rocprof_row(dom, B, H, W, khash) if dom.startswith("k_fast_cells") else None
         if rr:
             roof["rocprof"] = dict(rr, note="committed rocprofv3 --kernel-trace summary of this command on THIS build's kernel sources (builder-run, another box); "
                                             "the roofline's own time is avg_launch_ms, measured in this run")
             roof["rocprof"]["hip_events_over_rocprof"] = round(roof["avg_launch_ms"] / rr["rocprof_avg_ms"], 4) if rr["rocprof_avg_ms"] else None
+    if rank == 0:
+        step_ms = dt / args.steps * 1e3
         k_ms = 1e3 / args.steps
         result = {
             "metric": "ORB features/ms (+ frames/s), 640x480 8-level pyramid, 1000 features/frame",
@@ -950,7 +993,6 @@ def main():
                        "ms_per_step_min": round(min(dts) * k_ms, 4), "ms_per_step_max": round(max(dts) * k_ms, 4),
                        "ms_per_step_all": [round(v * k_ms, 4) for v in dts], "spread_frac": round((max(dts) - min(dts)) / dt, 4),
                        "timed_region_s": round(sum(dts), 4), "median_repeat_s": round(dt, 5)},
-            "verified_frames": int(vt.item()),
             "config": {"workload": f"S-EuRoC-640 batch replay: {B} frames/step/GPU of {W}x{H} u8, 8 levels sf 1.2, "
                                    f"nfeatures {args.nfeatures}, iniTh 20 minTh 7, mono lapping [0,1000]; frames resident in HBM, "
                                    f"results left in HBM; the steps rotate through {nsets} distinct batches ({nsets * B} distinct frames per GPU)",
@@ -969,9 +1011,11 @@ def main():
                        "scaling_mode": (f"strong: the same {args.streams} camera streams for every G, stream c -> GPU c mod G (SURVEY 8(e))" if args.streams > 0
                                         else "weak: one camera stream per GPU, per-GPU work fixed; SURVEY 8(e)'s fixed-8-stream curve is the `strong` record of this line"),
                        "parallelism": (f"{args.streams} camera streams over {world} GPUs" if args.streams > 0 else f"one camera stream per GPU x{world}")},
-            "roofline": roof,
         }
-        if exchange is None and world == 1 and not args.no_gather:
+        if args.full:
+            result["verified_frames"] = int(vt.item())
+            result["roofline"] = roof
+        if args.full and exchange is None and world == 1 and not args.no_gather:
             with stdout_to_stderr():
                 exchange = self_gather_exchange(ex, frame_sets, args, step_ms, sync_all)
         if exchange is not None:
@@ -979,7 +1023,7 @@ def main():
             result["exchange"] = exchange
         if strong is not None:
             result["strong"] = strong
-        if world == 1 and not args.no_frontend:
+        if args.full and world == 1 and not args.no_frontend:
             try:
                 fex = ORBextractor(args.nfeatures, 1.2, 8, 20, 7, device_id=local_rank)
                 fex.set_cpu_profile(args.profile, args.fma_build)
@@ -992,7 +1036,7 @@ def main():
                 result["streamed_frontend"] = {"error": str(e)[:300]}
             result["frame_constructor"] = frame_constructor()
             result["matcher_roofline"] = matcher_roofline(host_frames, args.nfeatures, [])
-        if world == 1 and not args.no_secondary:
+        if args.full and world == 1 and not args.no_secondary:
             result["end_to_end_operator"] = e2e_operator(host_frames, args.nfeatures)
             # ---- BASELINE config 4: TUM-VI shape, 1024x1024, 2000 features (large-image configuration)
             B4, H4, W4, NF4, steps4 = 64, 1024, 1024, 2000, 12
@@ -1013,7 +1057,7 @@ def main():
             eng4.close()
             del eng4, ex4, frames4
             result["secondary_natural"] = natural_leg(args, dev, local_rank, sync_all)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(host_frames[:64], args.nfeatures, args.cpu_budget)
         print(json.dumps(result), flush=True)
     if world > 1:

@@ -5,7 +5,7 @@
 cd "$(dirname "$0")/.."
 python -c "from orb_slam3_modified_amd.build import stamp; print(stamp())"
 for rep in 1 2 3; do for P in 1 2; do
-  echo "fast_passes $P (rep $rep): $(ORBX_FAST_PASSES=$P python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-frontend --no-fixed-streams 2>/dev/null | tail -1 | python -c "
+  echo "fast_passes $P (rep $rep): $(ORBX_FAST_PASSES=$P python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-frontend --no-fixed-streams 2>/dev/null | tail -1 | python -c "
 import sys,json; j=json.loads(sys.stdin.read()); print('step', j['ms_per_step'], 'min/max', j['timing']['ms_per_step_min'], j['timing']['ms_per_step_max'], 'value', j['value'], 'k_fast_cells', j['roofline']['kernels_ms_per_launch']['k_fast_cells'], '| natural', j['secondary_natural']['value'], 'k_fast_cells', j['secondary_natural']['kernels_ms_per_launch']['k_fast_cells'], '| config4', j['secondary']['value'])")"
 done; done
 for P in 1 2; do

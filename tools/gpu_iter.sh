@@ -9,7 +9,7 @@ mkdir -p gpurun_out
 python tools/kernel_times.py 256 2>/dev/null | tail -1
 python -m pytest tests/test_gpu_extractor.py -m gpu -x -q 2>&1 | tail -2
 for rep in 1 2; do
-  python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-frontend --no-fixed-streams --no-gather 2>/dev/null | tail -1 | python -c "
+  python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-frontend --no-fixed-streams --no-gather 2>/dev/null | tail -1 | python -c "
 import sys, json
 j = json.loads(sys.stdin.read())
 print('bench (rep $rep): step', j['ms_per_step'], 'value', j['value'], 'nat', j.get('secondary_natural', {}).get('value'), 'cfg4', j.get('secondary', {}).get('value'),

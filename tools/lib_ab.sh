@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 REPS=$1; shift
 run() {
   local label="$1"; shift
-  env "$@" python bench.py --steps 20 --warmup 5 --repeats 5 --no-cpu-baseline --no-frontend --no-fixed-streams --no-gather 2>/dev/null | tail -1 | python -c "
+  env "$@" python bench.py --full --steps 20 --warmup 5 --repeats 5 --no-cpu-baseline --no-frontend --no-fixed-streams --no-gather 2>/dev/null | tail -1 | python -c "
 import sys, json
 j = json.loads(sys.stdin.read())
 print('%-28s step %.4f (min %.4f max %.4f)  natural %.4f  config4 %.4f  verified %s  %s' % ('$label', j['ms_per_step'], j['timing']['ms_per_step_min'], j['timing']['ms_per_step_max'],

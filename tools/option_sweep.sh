@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 python -c "from orb_slam3_modified_amd.build import stamp; print(stamp())"
 run() {  # label, extra bench args, env assignments...
   local label="$1" extra="$2"; shift 2
-  env "$@" python bench.py --steps 20 --warmup 5 --repeats 5 --no-cpu-baseline --no-frontend --no-fixed-streams --no-gather --no-verify $extra 2>/dev/null | tail -1 | python -c "
+  env "$@" python bench.py --full --steps 20 --warmup 5 --repeats 5 --no-cpu-baseline --no-frontend --no-fixed-streams --no-gather --no-verify $extra 2>/dev/null | tail -1 | python -c "
 import sys, json
 j = json.loads(sys.stdin.read())
 print('%-44s step %.4f (min %.4f max %.4f)  natural %.4f  config4 %.4f' % ('$label', j['ms_per_step'], j['timing']['ms_per_step_min'], j['timing']['ms_per_step_max'],

@@ -16,7 +16,7 @@ for lm, one in ((0, 0), (1, 0), (0, 1), (1, 1)):
     ms, n = pr["k_quadtree"]
     print(f"level_major {lm} one_launch {one}: k_quadtree {1000*ms/max(n,1):.1f} us per 256 frames, same={dig==ref}", flush=True)
 for lm, one in ((0, 0), (1, 0), (1, 1)):
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "40", "--warmup", "5", "--no-secondary", "--no-cpu-baseline", "--no-frontend", "--no-verify"],
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "40", "--warmup", "5", "--no-secondary", "--no-cpu-baseline", "--no-frontend", "--no-verify"],
                        capture_output=True, text=True, env=dict(os.environ, ORBX_QT_LEVEL_MAJOR=str(lm), ORBX_QT_ONE_LAUNCH=str(one)))
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     print(f"bench level_major={lm} one_launch={one}: ms_per_step {j['ms_per_step']} value {j['value']}", flush=True)

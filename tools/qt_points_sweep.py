@@ -16,7 +16,7 @@ for pts in (2048, 1536, 1280, 1024, 768):
     ms, n = pr["k_quadtree"]
     print(f"qt_points {pts}: k_quadtree {1000*ms/max(n,1):.1f} us per 256 frames, same={dig==ref}", flush=True)
 for pts in (2048, 1536, 1024, 768):
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "30", "--warmup", "5", "--no-cpu-baseline", "--no-frontend", "--no-verify"],
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "30", "--warmup", "5", "--no-cpu-baseline", "--no-frontend", "--no-verify"],
                        capture_output=True, text=True, env=dict(os.environ, ORBX_QT_POINTS=str(pts)))
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     nat = j["secondary_natural"]
