@@ -26,6 +26,7 @@
 
 #include "orbx.h"
 #include "orbx_cv_compat.h"
+#include "orbx_train.h"
 
 // ---- DBoW2::BowVector / DBoW2::FeatureVector ---------------------------------------------------------------------------------
 // Inside the reference's tree (its root on the include path, as its CMakeLists.txt:83 has it) the reference's OWN two headers
@@ -193,6 +194,30 @@ class ORBVocabulary {
   void saveToBinaryFile(const std::string& filename) const {
     if (!voc_ || orbx_voc_save_binary(voc_, filename.c_str()) != ORBX_OK) throw std::runtime_error("ORBVocabulary::saveToBinaryFile failed");
   }
+  // TemplatedVocabulary::create(training_features, k, L, weighting, scoring) (TemplatedVocabulary.h:604-616): hierarchical k-means++ and
+  // the weights, with the k-means of the large nodes on the GPU (include/orbx_train.h).  Like the reference, this form seeds from the clock;
+  // the next one takes the seed of DUtils::Random::SeedRandOnce(seed) and reproduces the reference's tree for it.  Only a program that calls
+  // create has to link liborbx_train.so.  weighting / scoring are DBoW2::WeightingType / ScoringType values (0 = TF_IDF / L1_NORM), taken
+  // as int because some builds see the header before (or without) the enums' declaration.
+  void create(const std::vector<std::vector<cv::Mat> >& training_features, int k, int L, int weighting = 0, int scoring = 0) {
+    create(training_features, k, L, weighting, scoring, (uint32_t)std::chrono::system_clock::now().time_since_epoch().count());
+  }
+  void create(const std::vector<std::vector<cv::Mat> >& training_features, int k, int L, int weighting, int scoring, uint32_t seed,
+              orbx_train_stats* stats = nullptr) {
+    std::vector<uint8_t> desc;
+    std::vector<int64_t> off(1, 0);
+    for (const auto& doc : training_features) {
+      for (const auto& m : doc) desc.insert(desc.end(), m.ptr<unsigned char>(), m.ptr<unsigned char>() + 32);
+      off.push_back((int64_t)(desc.size() / 32));
+    }
+    const orbx_train_params p = {k, L, weighting, scoring, seed, -1, 0};
+    orbx_voc* v = nullptr;
+    if (orbx_train_vocabulary(ctx_, desc.data(), off.data(), (int)training_features.size(), &p, &v, stats) != ORBX_OK)
+      throw std::runtime_error(std::string("ORBVocabulary::create: ") + orbx_train_last_error());
+    orbx_voc_destroy(voc_);
+    voc_ = v;
+  }
+
   unsigned int size() const { int w = 0; if (voc_) orbx_voc_info(voc_, nullptr, nullptr, nullptr, &w); return (unsigned)w; }
   bool empty() const { return size() == 0; }
 

@@ -1,5 +1,6 @@
 """Host-side mirror of ORB_SLAM3::ORBVocabulary = DBoW2::TemplatedVocabulary<cv::Mat, FORB>
-(reference include/ORBVocabulary.h:27-29): loadFromTextFile, transform (tree descent on the GPU), score."""
+(reference include/ORBVocabulary.h:27-29): loadFromTextFile, transform (tree descent on the GPU), score, and create (training,
+liborbx_train.so)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -7,7 +8,11 @@ from typing import Dict, List, Tuple
 
 import numpy as np
 
-from ._lib import OrbxError, check, lib, ptr
+from ._lib import OrbxError, OrbxTrainParams, OrbxTrainStats, check, lib, ptr, train_lib
+
+# DBoW2::WeightingType / ScoringType (BowVector.h:40-57)
+TF_IDF, TF, IDF, BINARY = 0, 1, 2, 3
+L1_NORM, L2_NORM, CHI_SQUARE, KL, BHATTACHARYYA, DOT_PRODUCT = 0, 1, 2, 3, 4, 5
 
 
 class ORBVocabulary:
@@ -38,6 +43,27 @@ class ORBVocabulary:
             return False
         self._voc = v
         return True
+
+    def create(self, docs, k: int = 10, L: int = 5, weighting: int = TF_IDF, scoring: int = L1_NORM, seed: int = 0,
+               device_min_node: int = -1, max_iterations: int = 0) -> dict:
+        """TemplatedVocabulary::create(training_features, k, L, weighting, scoring) (TemplatedVocabulary.h:558-616) after
+        DUtils::Random::SeedRandOnce(seed): `docs` is a list of (n_i, 32) uint8 arrays, one per document.  Replaces the vocabulary
+        held; returns the training stats (orbx_train_stats) as a dict.  device_min_node / max_iterations: include/orbx_train.h."""
+        arrs = [np.ascontiguousarray(d, np.uint8).reshape(-1, 32) for d in docs]
+        offs = np.zeros(len(arrs) + 1, np.int64)
+        offs[1:] = np.cumsum([len(a) for a in arrs]) if arrs else []
+        desc = np.ascontiguousarray(np.concatenate(arrs) if arrs else np.zeros((0, 32), np.uint8))
+        T = train_lib()
+        p = OrbxTrainParams(k, L, weighting, scoring, seed & 0xFFFFFFFF, device_min_node, max_iterations)
+        st = OrbxTrainStats()
+        v = C.c_void_p(0)
+        rc = T.orbx_train_vocabulary(self._ctx, ptr(desc), ptr(offs), len(arrs), C.byref(p), C.byref(v), C.byref(st))
+        if rc != 0:
+            raise OrbxError(rc, T.orbx_train_last_error().decode())
+        if self._voc and self._voc.value:
+            self._L.orbx_voc_destroy(self._voc)
+        self._voc = v
+        return st.as_dict()
 
     def saveToTextFile(self, filename: str) -> None:
         """TemplatedVocabulary.h:1428-1449 (byte-identical to the reference's writer)."""
