@@ -97,3 +97,41 @@ def make_camera_streams(n_cams: int, n_frames: int, height: int = 480, width: in
                         seed: int = DEFAULT_SEED) -> np.ndarray:
     """S-8cam: independent streams with seeds +1000*cam. uint8 [n_cams, n_frames, height, width]."""
     return np.stack([make_stream(n_frames, height, width, seed + 1000 * c) for c in range(n_cams)])
+
+
+def make_stereo_pairs(n_pairs: int, height: int = 480, width: int = 752, seed: int = DEFAULT_SEED, n_rects: int = 6,
+                      background: int = 8, min_disp: int = 2, max_disp: int = 60, noise: int = 0):
+    """Rectified stereo pairs with a piecewise disparity map: the left frames are make_stream's; the right frame is the left one warped by
+    a background disparity plus `n_rects` rectangles at min_disp .. max_disp px (the nearer layer wins where they overlap, as a closer surface
+    hides a farther one), the pixels no layer reaches (occlusions) filled from their left neighbour along the row, then +-`noise` per pixel.
+    Returns (left [n, h, w], right [n, h, w], disparity [n, h, w] int32 of every LEFT pixel: its match sits at x - disparity)."""
+    left = make_stream(n_pairs, height, width, seed)
+    rng = np.random.default_rng(seed + 7919)
+    right = np.empty_like(left)
+    disp = np.empty(left.shape, np.int32)
+    cols = np.arange(width)
+    for t in range(n_pairs):
+        d = np.full((height, width), background, np.int32)
+        for _ in range(n_rects):
+            rh, rw = int(rng.integers(height // 8, height // 3)), int(rng.integers(width // 10, width // 4))
+            y0, x0 = int(rng.integers(0, height - rh)), int(rng.integers(0, width - rw))
+            v = int(rng.integers(min_disp, max_disp + 1))
+            d[y0:y0 + rh, x0:x0 + rw] = np.maximum(d[y0:y0 + rh, x0:x0 + rw], v)
+        disp[t] = d
+        out = np.zeros((height, width), np.uint8)
+        have = np.zeros((height, width), bool)
+        for v in np.unique(d):   # far to near: a nearer layer overwrites
+            ys, xs = np.nonzero(d == v)
+            xr = xs - v
+            ok = xr >= 0
+            out[ys[ok], xr[ok]] = left[t][ys[ok], xs[ok]]
+            have[ys[ok], xr[ok]] = True
+        src = np.where(have, cols[None, :], -1)
+        src = np.maximum.accumulate(src, axis=1)                      # last written pixel at or left of x
+        first = np.argmax(have, axis=1)                               # rows start with a hole: take the row's first written pixel
+        src = np.where(src < 0, first[:, None], src)
+        img = np.take_along_axis(out, src, axis=1)
+        if noise:
+            img = np.clip(img.astype(np.int32) + rng.integers(-noise, noise + 1, img.shape), 0, 255).astype(np.uint8)
+        right[t] = img
+    return left, right, disp

@@ -1,0 +1,141 @@
+#!/usr/bin/env python3
+"""Batched stereo front-end times (liborbx_stereo.so) -> profiles/stereo_batch_times_r7.txt.
+
+256 synthetic rectified pairs (synth.make_stereo_pairs, noise 2) at the EuRoC shape (752 x 480; 1200 features, 1.2, 8 levels, 20 / 7; mb 0.11,
+mbf 47.906) and at the KITTI shape (1241 x 376; 2000 features; mbf = 0.53716 * 718.856), frames resident in HBM.  HIP-event timings on one
+stream, `--repeats` times after two warm-up runs; median and [min, max] per leg:
+  (a) the two batch extractions alone (left on the stream, right on a second stream, forked and joined by events: the one-call form's shape)
+  (b) orbx_stereo_extract_batch_device (both extractions + the association)
+  (c) the association kernels alone (orbx_stereo_match_batch_device on the resident results)
+  (d) today's per-pair loop over 64 pairs: orbx_extract x 2 + orbx_stereo_matches (host buffers, wall clock)
+  (e) the oracle's restatement of ComputeStereoMatches on one core per pair (wall clock, the pyramids already on the host)
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+OUT = os.path.join(ROOT, "profiles", "stereo_batch_times_r7.txt")
+CONFIGS = {
+    "euroc_752x480": dict(shape=(480, 752), params=(1200, 1.2, 8, 20, 7), mb=0.11, mbf=47.90639384423901),
+    "kitti_1241x376": dict(shape=(376, 1241), params=(2000, 1.2, 8, 20, 7), mb=0.53716, mbf=0.53716 * 718.856),
+}
+
+
+def stats(v):
+    v = np.asarray(v, np.float64)
+    return {"median": round(float(np.median(v)), 4), "min": round(float(v.min()), 4), "max": round(float(v.max()), 4), "n": int(len(v))}
+
+
+def run(name, cfg, B, repeats, device_only=False):
+    import torch
+    from oracle import pyoracle as po
+    from orb_slam3_modified_amd import ORBextractor, ORBmatcher, synth
+    from orb_slam3_modified_amd.stereo import StereoBatch
+    H, W = cfg["shape"]
+    L, R, _ = synth.make_stereo_pairs(B, H, W, seed=7, noise=2)
+    exL = ORBextractor(*cfg["params"], device_id=0)
+    exR = exL.clone()
+    sb = StereoBatch(exL, exR, cfg["mb"], cfg["mbf"])
+    cap = exL.capacity
+    dev = torch.device("cuda:0")
+    s, s2 = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
+    tL, tR = torch.from_numpy(L).to(dev), torch.from_numpy(R).to(dev)
+    z = lambda *shape, dt=torch.uint8: torch.zeros(shape, dtype=dt, device=dev)   # noqa: E731
+    kL, dL, cL, kR, dR, cR = z(B, cap, 28), z(B, cap, 32), z(B, 2, dt=torch.int32), z(B, cap, 28), z(B, cap, 32), z(B, 2, dt=torch.int32)
+    u, d, k = z(B, cap, dt=torch.float32), z(B, cap, dt=torch.float32), z(B, dt=torch.int32)
+    p = lambda t: t.data_ptr()   # noqa: E731
+    torch.cuda.synchronize()
+
+    def leg_a():
+        fork, join = torch.cuda.Event(), torch.cuda.Event()
+        fork.record(s)
+        s2.wait_event(fork)
+        exL.extract_batch_device(p(tL), B, H, W, W, H * W, p(kL), p(dL), p(cL), stream=s.cuda_stream)
+        exR.extract_batch_device(p(tR), B, H, W, W, H * W, p(kR), p(dR), p(cR), stream=s2.cuda_stream)
+        join.record(s2)
+        s.wait_event(join)
+
+    def leg_b():
+        sb.extract_device(p(tL), p(tR), B, H, W, W, H * W, p(kL), p(dL), p(cL), p(kR), p(dR), p(cR), p(u), p(d), p(k), stream=s.cuda_stream)
+
+    def leg_c():
+        sb.match_device(B, p(kL), p(dL), p(cL), p(kR), p(dR), p(cR), p(u), p(d), p(k), stream=s.cuda_stream)
+
+    res = {"pairs": B, "capacity": cap}
+    for leg, fn in (("a_two_extractions_ms", leg_a), ("b_stereo_extract_batch_device_ms", leg_b), ("c_association_ms", leg_c)):
+        ts = []
+        for i in range(repeats + 2):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(s)
+            fn()
+            e1.record(s)
+            e1.synchronize()
+            if i >= 2:
+                ts.append(e0.elapsed_time(e1))
+        res[leg] = stats(ts)
+    torch.cuda.synchronize()
+    kept = k.cpu().numpy()
+    res["kept_median"] = int(np.median(kept))
+    res["features_per_pair_left"] = int(np.median(cL.cpu().numpy()[:, 0]))
+    if device_only:
+        sb.close()
+        return res
+    # (d) per pair, host buffers: two single-frame extractions + orbx_stereo_matches
+    x1, x2 = exL.clone(), exL.clone()
+    n = min(64, B)
+    ts = []
+    for rep in range(3):
+        t0 = time.perf_counter()
+        for f in range(n):
+            _, a1, b1 = x1(L[f], None, (0, 0))
+            _, a2, b2 = x2(R[f], None, (0, 0))
+            ORBmatcher.ComputeStereoMatches(x1, x2, a1, b1, a2, b2, cfg["mb"], cfg["mbf"])
+        ts.append((time.perf_counter() - t0) * 1e3 / n)
+    res["d_per_pair_loop_ms_per_pair"] = stats(ts)
+    res["d_per_pair_loop_ms_256_equivalent"] = round(float(np.median(ts)) * B, 2)
+    # (e) the oracle on one core, per pair
+    ts = []
+    for f in range(16):
+        _, a1, b1 = x1(L[f], None, (0, 0))
+        _, a2, b2 = x2(R[f], None, (0, 0))
+        pl, pr = x1.mvImagePyramid, x2.mvImagePyramid
+        t0 = time.perf_counter()
+        po.stereo_matches(a1, b1, a2, b2, pl, pr, x1.GetScaleFactors(), x1.GetInverseScaleFactors(), cfg["mb"], cfg["mbf"])
+        ts.append((time.perf_counter() - t0) * 1e3)
+    res["e_oracle_one_core_ms_per_pair"] = stats(ts)
+    a, b, c = (res[x]["median"] for x in ("a_two_extractions_ms", "b_stereo_extract_batch_device_ms", "c_association_ms"))
+    res["b_minus_a_over_a"] = round((b - a) / a, 4)
+    res["c_over_a"] = round(c / a, 4)
+    sb.close()
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--pairs", type=int, default=256)
+    ap.add_argument("--repeats", type=int, default=10)
+    ap.add_argument("--out", default=OUT)
+    ap.add_argument("--device-only", action="store_true", help="legs (a) - (c) only (counter collection runs)")
+    args = ap.parse_args()
+    from orb_slam3_modified_amd import build
+    out = {"stamp": build.stamp(), "repeats": args.repeats}
+    for name, cfg in CONFIGS.items():
+        out[name] = run(name, cfg, args.pairs, args.repeats, args.device_only)
+        print(name, json.dumps(out[name]), flush=True)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as fh:
+        fh.write("# tools/stereo_batch_times.py: batched stereo front-end, HIP-event medians [min, max] of --repeats runs (ms)\n")
+        fh.write(json.dumps(out, indent=1) + "\n")
+    print("wrote", args.out)
+
+
+if __name__ == "__main__":
+    main()
