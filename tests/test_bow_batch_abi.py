@@ -1,0 +1,102 @@
+"""include/orbx_bow.h <-> liborbx_bow.so: the batched bag of words is a library of its own beside the product (CPU-only checks)."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+import tempfile
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+KERNELS_HASH = "eee3be0e614ece87"   # the product's kernel sources: this library changes none of them
+
+
+def _declared(header):
+    h = open(os.path.join(ROOT, "include", header)).read()
+    h = re.sub(r"/\*.*?\*/", "", h, flags=re.S)
+    return sorted(set(re.findall(r"\b(orbx_[a-z0-9_]+)\s*\(", h)))
+
+
+def _exported(path):
+    out = subprocess.check_output(["nm", "-D", "--defined-only", path]).decode()
+    return {l.split()[-1] for l in out.splitlines() if " T " in l}
+
+
+def test_build_produces_the_bow_library():
+    from orb_slam3_modified_amd import _lib, build
+    build.build()
+    assert os.path.isfile(build.BOW_OUT) and build.BOW_OUT == _lib.BOW_LIB_PATH
+    assert os.path.dirname(build.BOW_OUT) == os.path.dirname(_lib.LIB_PATH) == os.path.join(ROOT, "orb_slam3_modified_amd")
+    assert os.path.basename(build.BOW_OUT) == "liborbx_bow.so"
+
+
+def test_bow_library_exports_exactly_its_header():
+    from orb_slam3_modified_amd import _lib, build
+    build.build()
+    names = _declared("orbx_bow.h")
+    assert len(names) == 7 and all(n.startswith("orbx_bow_") for n in names), names
+    exported = _exported(_lib.BOW_LIB_PATH)
+    assert {e for e in exported if e.startswith("orbx_")} == set(names)
+    assert not [e for e in exported if not e.startswith("orbx_bow_") and not e.startswith("_")], sorted(exported)[:10]   # -fvisibility=hidden
+
+
+def test_product_library_keeps_its_abi_and_its_kernels():
+    from orb_slam3_modified_amd import _lib, build
+    build.build()
+    bnames = set(_declared("orbx_bow.h"))
+    assert not bnames & _exported(_lib.LIB_PATH), "liborbx.so exports a batched bag-of-words entry point"
+    assert not bnames & set(_declared("orbx.h"))
+    assert len(_declared("orbx.h")) <= 100
+    assert build.kernels_hash() == KERNELS_HASH
+    assert os.path.dirname(build.BOW_SOURCE) == "bow" and "orbx_bow.hip" not in os.listdir(build.CSRC)
+
+
+def test_python_binding_covers_the_header():
+    from orb_slam3_modified_amd import _lib, build
+    build.build()
+    B = _lib.bow_lib()
+    assert set(B._orbx_bow_symbols) == set(_declared("orbx_bow.h"))
+    from orb_slam3_modified_amd import bow
+    for m in ("transform", "transform_device", "score_matrix", "score_matrix_device"):
+        assert callable(getattr(bow.BowBatch, m))
+
+
+def test_create_rejects_bad_arguments_without_a_device():
+    """Argument checks that come before any device call."""
+    from orb_slam3_modified_amd import _lib
+    B = _lib.bow_lib()
+    h = C.c_void_p(0)
+    assert B.orbx_bow_create(C.byref(h), None, 4) == _lib.ORBX_E_INVALID and not h.value
+    assert b"null" in B.orbx_bow_last_error(None)
+    assert B.orbx_bow_create(None, None, 4) == _lib.ORBX_E_INVALID
+    assert B.orbx_bow_transform_batch_device(None, *([None] * 2), 1, 1, *([None] * 8)) == _lib.ORBX_E_INVALID
+    assert B.orbx_bow_score_matrix_device(None, None, None, None, 1, 1, None, None, None, 1, 1, None, None) == _lib.ORBX_E_INVALID
+    B.orbx_bow_destroy(None)
+
+
+@pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not installed")
+def test_bow_kernels_compile_without_scratch():
+    from orb_slam3_modified_amd.build import BOW_SOURCE, CSRC, FLAGS
+    flags = [f for f in FLAGS if f not in ("-shared", "-fPIC", "-ldl")] + ["-fvisibility=hidden"]
+    tmp = tempfile.mkdtemp(prefix="orbx_bow_asm_")
+    out = os.path.join(tmp, "bow.s")
+    try:
+        p = subprocess.run(["hipcc"] + flags + ["-S", "--cuda-device-only", "-o", out, os.path.join(CSRC, BOW_SOURCE)],
+                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        assert p.returncode == 0, p.stdout[-2000:]
+        scratch = {}
+        name = None
+        for line in open(out):
+            m = re.match(r"\s*\.amdhsa_kernel\s+(\S+)", line)
+            if m:
+                name = m.group(1)
+            m = re.match(r"\s*\.amdhsa_private_segment_fixed_size\s+(\d+)", line)
+            if m:
+                scratch[name] = int(m.group(1))
+        for k in ("k_bowb_frame", "k_bowb_score"):
+            hit = [n for n in scratch if k in n]
+            assert len(hit) == 1, (k, sorted(scratch))
+        assert all(v == 0 for v in scratch.values()), scratch
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)

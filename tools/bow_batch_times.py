@@ -1,0 +1,175 @@
+#!/usr/bin/env python3
+"""Batched bag-of-words times (liborbx_bow.so) -> profiles/bow_batch_times_r8.txt.
+
+256 synthetic frames at the EuRoC shape (752 x 480; 1000 features, 1.2, 8 levels, 20 / 7) resident in HBM, a k = 10, L = 6 tree trained on
+> 10^6 descriptors (ORBVocabulary.create), levelsup 4.  HIP-event timings on one stream, `--repeats` times after three warm-up runs; median
+and [min, max] per leg:
+  (x) the batch extraction that produces the descriptors (orbx_extract_batch_device)
+  (a) orbx_bow_transform_batch_device: descent + BowVectors + FeatureVectors
+  (a1) the descent alone (orbx_bow_transform_device over all frames x capacity rows)   (a2) (a) without FeatureVectors   (a3) (a) without BowVectors
+  (b) the per-frame loop of before: orbx_bow_transform + orbx_bow_finalize per frame on host descriptors (wall clock, C calls only)
+  (c) orbx_bow_score_matrix_device 256 x 256 and 256 x 4096   (d) the loop of orbx_bow_score_l1_batch calls for the same scores (wall clock)
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+OUT = os.path.join(ROOT, "profiles", "bow_batch_times_r8.txt")
+
+
+def stats(v):
+    v = np.asarray(v, np.float64)
+    return {"median": round(float(np.median(v)), 4), "min": round(float(v.min()), 4), "max": round(float(v.max()), 4), "n": int(len(v))}
+
+
+def clocks():
+    """The GPU's clock state as the driver reports it (read only)."""
+    try:
+        out = subprocess.run(["rocm-smi", "-d", "0", "--showclocks", "--showperflevel"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
+                             timeout=30).stdout
+        return [l.strip() for l in out.splitlines() if "GPU[0]" in l and ("sclk" in l or "mclk" in l or "Performance" in l)]
+    except Exception as e:   # noqa: BLE001
+        return [f"not read: {e}"]
+
+
+def run(B, repeats, train_frames):
+    import torch
+    from orb_slam3_modified_amd import ORBextractor, ORBVocabulary, _lib, synth
+    from orb_slam3_modified_amd._lib import ptr
+    from orb_slam3_modified_amd.bow import BowBatch
+    H, W, params, levelsup = 480, 752, (1000, 1.2, 8, 20, 7), 4
+    ex = ORBextractor(*params, device_id=0)
+    cap = ex.capacity
+    dev = torch.device("cuda:0")
+    s = torch.cuda.Stream(device=dev)
+    imgs = synth.make_stream(B, H, W)
+    t = torch.from_numpy(imgs).to(dev)
+    z = lambda *shape, dt=torch.uint8: torch.zeros(shape, dtype=dt, device=dev)   # noqa: E731
+    kps, desc, counts = z(B, cap, 28), z(B, cap, 32), z(B, 2, dt=torch.int32)
+    p = lambda x: x.data_ptr()   # noqa: E731
+    # the tree
+    trainer, docs = ex.clone(), []
+    for a in range(0, train_frames, 64):
+        docs += [r[2] for r in trainer.extract_batch(synth.make_stream(64, 480, 640, 9000 + a), (0, 1000))]
+    gv = ORBVocabulary(ex)
+    t0 = time.perf_counter()
+    gv.create(docs, 10, 6, 0, 0, seed=2024)
+    res = {"frames": B, "capacity": cap, "levelsup": levelsup, "training_descriptors": int(sum(len(d) for d in docs)), "tree": gv.info(),
+           "create_wall_ms": round((time.perf_counter() - t0) * 1e3, 1)}
+    bb = BowBatch(gv, levelsup)
+    L = _lib.lib()
+    word, node, weight = z(B * cap, dt=torch.int32), z(B * cap, dt=torch.int32), z(B * cap, dt=torch.float64)
+    out = None
+
+    def leg_x():
+        ex.extract_batch_device(p(t), B, H, W, W, H * W, p(kps), p(desc), p(counts), (0, 1000), stream=s.cuda_stream)
+
+    def leg_a():
+        nonlocal out
+        out = bb.transform_device(desc, counts, B, cap, out=out, stream=s.cuda_stream)
+
+    def leg_a1():
+        _lib.check(L.orbx_bow_transform_device(gv._voc, ptr(p(desc)), B * cap, levelsup, ptr(p(word)), ptr(p(weight)), ptr(p(node)), ptr(s.cuda_stream)))
+
+    def leg_a2():
+        bb.transform_device(desc, counts, B, cap, out=out, stream=s.cuda_stream, fv=False)
+
+    def leg_a3():
+        bb.transform_device(desc, counts, B, cap, out=out, stream=s.cuda_stream, bow=False)
+
+    def timed(fn, n):
+        ts = []
+        for i in range(n + 3):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(s)
+            fn()
+            e1.record(s)
+            e1.synchronize()
+            if i >= 3:
+                ts.append(e0.elapsed_time(e1))
+        return stats(ts)
+
+    torch.cuda.synchronize()
+    res["x_extract_batch_device_ms"] = timed(leg_x, repeats)
+    for name, fn in (("a_transform_batch_device_ms", leg_a), ("a1_descent_all_rows_ms", leg_a1), ("a2_descent_and_bowvectors_ms", leg_a2),
+                     ("a3_descent_and_featurevectors_ms", leg_a3)):
+        res[name] = timed(fn, repeats)
+    torch.cuda.synchronize()
+    hd, hc = desc.cpu().numpy(), counts.cpu().numpy()
+    res["features_per_frame_median"] = int(np.median(hc[:, 0]))
+    res["bow_entries_per_frame_median"] = int(np.median(out.bow_n.cpu().numpy()))
+    res["fv_nodes_per_frame_median"] = int(np.median(out.fv_n.cpu().numpy()))
+    # (b) the per-frame loop over the existing entry points (C calls only: no FeatureVector is built on the host here)
+    rows = [np.ascontiguousarray(hd[f, :hc[f, 0]]) for f in range(B)]
+    w_, n_, wt_ = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32), np.zeros(cap, np.float64)
+    ids_, vals_, k_ = np.zeros(cap, np.uint32), np.zeros(cap, np.float64), C.c_int(0)
+    ts = []
+    for rep in range(7):
+        t0 = time.perf_counter()
+        for d in rows:
+            L.orbx_bow_transform(gv._voc, ptr(d), len(d), levelsup, ptr(w_), ptr(wt_), ptr(n_))
+            L.orbx_bow_finalize(gv._voc, ptr(w_), ptr(wt_), len(d), ptr(ids_), ptr(vals_), C.byref(k_))
+        ts.append((time.perf_counter() - t0) * 1e3)
+    res["b_per_frame_loop_ms"] = stats(ts[2:])
+    a, b, x = res["a_transform_batch_device_ms"]["median"], res["b_per_frame_loop_ms"]["median"], res["x_extract_batch_device_ms"]["median"]
+    res["b_over_a"] = round(b / a, 2)
+    res["a_over_x"] = round(a / x, 4)
+    # (c) score matrices: the batch against itself and against 4096 vectors (the batch repeated)
+    rep = 4096 // B
+    db_ids, db_vals, db_n = out.bow_ids.repeat(rep, 1), out.bow_vals.repeat(rep, 1), out.bow_n.repeat(rep)
+    ndb = db_n.shape[0]
+    sc1, sc2 = z(B, B, dt=torch.float64), z(B, ndb, dt=torch.float64)
+    res["c_score_matrix_BxB_ms"] = timed(lambda: bb.score_matrix_device(out.bow_ids, out.bow_vals, out.bow_n, B, cap, out.bow_ids, out.bow_vals,
+                                                                         out.bow_n, B, cap, scores=sc1, stream=s.cuda_stream), repeats)
+    res["c_score_matrix_Bx%d_ms" % ndb] = timed(lambda: bb.score_matrix_device(out.bow_ids, out.bow_vals, out.bow_n, B, cap, db_ids, db_vals, db_n,
+                                                                               ndb, cap, scores=sc2, stream=s.cuda_stream), repeats)
+    torch.cuda.synchronize()
+    vecs = [r[0] for r in out.frames()]
+    ts = []
+    for r_ in range(3):
+        t0 = time.perf_counter()
+        got = [gv.score_batch(q, vecs) for q in vecs]
+        ts.append((time.perf_counter() - t0) * 1e3)
+    res["d_score_l1_batch_loop_BxB_ms"] = stats(ts)
+    assert np.array(got).tobytes() == sc1.cpu().numpy().tobytes(), "score matrix != the loop of orbx_bow_score_l1_batch"
+    big = vecs * rep
+    t0 = time.perf_counter()
+    nq_d = min(32, B)
+    for q in vecs[:nq_d]:
+        gv.score_batch(q, big)
+    res["d_score_l1_batch_loop_Bx%d_ms_extrapolated_from_%d_queries" % (ndb, nq_d)] = round((time.perf_counter() - t0) * 1e3 * B / nq_d, 1)
+    bb.close()
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=256)
+    ap.add_argument("--repeats", type=int, default=50)
+    ap.add_argument("--train-frames", type=int, default=1088, help="480 x 640 frames whose descriptors train the tree (1088 -> > 10^6)")
+    ap.add_argument("--out", default=OUT)
+    args = ap.parse_args()
+    from orb_slam3_modified_amd import build
+    out = {"stamp": build.stamp(), "repeats": args.repeats, "clocks_before": clocks()}
+    out["euroc_752x480"] = run(args.frames, args.repeats, args.train_frames)
+    out["clocks_after"] = clocks()
+    print(json.dumps(out), flush=True)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as fh:
+        fh.write("# tools/bow_batch_times.py: batched bag of words, HIP-event medians [min, max] of --repeats runs (ms); (b), (d): wall clock\n")
+        fh.write(json.dumps(out, indent=1) + "\n")
+    print("wrote", args.out)
+
+
+if __name__ == "__main__":
+    main()
