@@ -3,7 +3,6 @@ frames at once on descriptors resident in HBM (a batch extraction's buffers, a r
 pair of two batches.  All arithmetic runs in the HIP kernels of the library; this file only marshals buffers."""
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -52,34 +51,13 @@ class BowDeviceResult:
         return out
 
 
-class BowBatch:
+class BowBatch(_lib.SideHandle):
     """BowVectors, FeatureVectors and L1 score matrices for batches of frames with one ORBVocabulary (which must stay alive)."""
 
     def __init__(self, vocabulary, levelsup: int = 4):
         self._B = _lib.bow_lib()
-        self._h = C.c_void_p(0)
         self.vocabulary, self.levelsup = vocabulary, int(levelsup)
-        rc = self._B.orbx_bow_create(C.byref(self._h), vocabulary._voc, int(levelsup))
-        if rc != 0:
-            m = self._B.orbx_bow_last_error(None)
-            raise _lib.OrbxError(rc, m.decode() if m else "")
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._B.orbx_bow_destroy(self._h)
-            self._h = C.c_void_p(0)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc: int) -> int:
-        if rc < 0:
-            m = self._B.orbx_bow_last_error(self._h)
-            raise _lib.OrbxError(rc, m.decode() if m else "")
-        return rc
+        super().__init__(self._B, "orbx_bow", vocabulary._voc, int(levelsup))
 
     # ---- transform ---------------------------------------------------------------------------------------
     def transform(self, desc: np.ndarray, counts: np.ndarray) -> list:

@@ -1,32 +1,49 @@
-"""In-tree build of liborbx.so — the product —, of liborbx_train.so — vocabulary training (include/orbx_train.h) —, of liborbx_stereo.so — the
-batched stereo front-end (include/orbx_stereo.h) —, of liborbx_bow.so — the batched bag of words (include/orbx_bow.h) — and of liborbx_debug.so — the diagnostic ABI (include/orbx_debug.h: stage dumps and numeric test
-hooks for the parity tests and the profiling tools; the product library has none of them).  HIP, gfx950 only.
-`python -m orb_slam3_modified_amd.build [--force]`."""
+"""In-tree build of the project's shared libraries.  HIP, gfx950 only.  `python -m orb_slam3_modified_amd.build [--force]`.
+
+LIBS is the one place that knows them, one record per library; what is stale, what is compiled and what is linked all follow from it:
+  liborbx.so         the product (include/orbx.h): the top level of csrc/, which kernels_hash() stamps
+  liborbx_debug.so   the diagnostic ABI (include/orbx_debug.h): stage dumps and numeric test hooks for the parity tests and the profiling
+                     tools; the product library has none of them
+  liborbx_train.so   vocabulary training (include/orbx_train.h)
+  liborbx_stereo.so  the batched stereo front-end (include/orbx_stereo.h)
+  liborbx_bow.so     the batched bag of words (include/orbx_bow.h)
+The libraries beside the product link liborbx.so and use its ABI (and orbx_internal.h where they read a context's buffers).  Their sources sit
+in subdirectories of csrc/, outside kernels_hash(): the committed counter files measure the product's kernels, which they do not change.
+A new one is one more record ("Adding a side library")."""
 from __future__ import annotations
 
 import os
 import subprocess
 import sys
+from typing import NamedTuple
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.environ.get("ORBX_BUILD_OUT") or os.path.join(HERE, "liborbx.so")   # ORBX_BUILD_OUT (+ ORBX_EXTRA_FLAGS): experiment builds beside the product
 SOURCES = ["orbx_extractor.hip", "orbx_matcher.hip", "orbx_search.hip", "orbx_window.hip", "orbx_kfdb.hip", "orbx_replay.hip"]
 DEBUG_OUT = os.path.join(os.path.dirname(OUT), "liborbx_debug.so")
-DEBUG_SOURCE = "orbx_debug.hip"     # = the extractor's translation unit with ORBX_DEBUG_ABI; -fvisibility=hidden: exports orbx_debug_* alone
-# liborbx_train.so — vocabulary training (include/orbx_train.h): offline work beside the product, links liborbx.so and uses only its ABI.  Its
-# source sits in csrc/train/, outside kernels_hash(): the committed counter files measure the product's kernels, which it does not change.
+DEBUG_SOURCE = "orbx_debug.hip"     # = the extractor's translation unit with ORBX_DEBUG_ABI
 TRAIN_OUT = os.path.join(os.path.dirname(OUT), "liborbx_train.so")
 TRAIN_SOURCE = os.path.join("train", "orbx_train.hip")
-# liborbx_stereo.so — the batched stereo front-end (include/orbx_stereo.h): links liborbx.so for the product calls it makes and reads the buffers a
-# product context left behind (orbx_internal.h), like the debug library; -fvisibility=hidden: exports orbx_stereo_* alone.  Source in csrc/stereo/,
-# outside kernels_hash() for the same reason as the training library's.
 STEREO_OUT = os.path.join(os.path.dirname(OUT), "liborbx_stereo.so")
 STEREO_SOURCE = os.path.join("stereo", "orbx_stereo.hip")
-# liborbx_bow.so — the batched bag of words (include/orbx_bow.h): BowVectors, FeatureVectors and L1 score matrices for B frames.  Built exactly like
-# the stereo library: links liborbx.so, -fvisibility=hidden (exports orbx_bow_* alone), source in csrc/bow/, outside kernels_hash().
 BOW_OUT = os.path.join(os.path.dirname(OUT), "liborbx_bow.so")
 BOW_SOURCE = os.path.join("bow", "orbx_bow.hip")
+
+
+class Lib(NamedTuple):
+    out: str
+    sources: tuple          # relative to csrc/, one object each
+    hidden: bool = False    # -fvisibility=hidden: the library exports its extern "C" entry points alone
+    product: bool = False   # links liborbx.so: what it takes from the product it takes at load time ($ORIGIN)
+    deps: tuple = ()        # further files of csrc/ its objects are made from
+
+
+LIBS = (Lib(OUT, tuple(SOURCES)),
+        Lib(DEBUG_OUT, (DEBUG_SOURCE,), hidden=True, product=True, deps=("orbx_extractor.hip",)),   # it IS the extractor's translation unit
+        Lib(TRAIN_OUT, (TRAIN_SOURCE,), product=True),
+        Lib(STEREO_OUT, (STEREO_SOURCE,), hidden=True, product=True),
+        Lib(BOW_OUT, (BOW_SOURCE,), hidden=True, product=True))
 HEADERS = ("orbx.h", "orbx_debug.h", "orbx_train.h", "orbx_stereo.h", "orbx_bow.h")
 # -ffp-contract=off: the float paths (fastAtan2 polynomial, BRIEF rotation) must not be fused into FMAs,
 # the CPU reference evaluates them as separate IEEE operations (DESIGN.md "bit-exactness").
@@ -57,60 +74,59 @@ def stamp() -> dict:
     return {"kernels_hash": kernels_hash(), "commit": commit, "date": datetime.datetime.utcnow().strftime("%Y-%m-%dT%H:%MZ")}
 
 
+def _headers(below: bool) -> list:
+    """What an object may include: include/, the headers of csrc/'s top level and, for a source in a subdirectory of csrc/, those of every
+    subdirectory too (csrc/side/)."""
+    hs = [os.path.join(HERE, "..", "include", h) for h in HEADERS]
+    for d, _, files in os.walk(CSRC):
+        if below or d == CSRC:
+            hs += [os.path.join(d, f) for f in files if f.endswith((".h", ".inc")) or f == "orbx_kernels.hip"]
+    return hs
+
+
 def _stale() -> bool:
-    outs = (OUT, DEBUG_OUT, TRAIN_OUT, STEREO_OUT, BOW_OUT)
-    if not all(os.path.exists(o) for o in outs):
+    if not all(os.path.exists(lib.out) for lib in LIBS):
         return True
-    t = min(os.path.getmtime(o) for o in outs)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(CSRC, TRAIN_SOURCE), os.path.join(CSRC, STEREO_SOURCE), os.path.join(CSRC, BOW_SOURCE)] + \
-           [os.path.join(HERE, "..", "include", h) for h in HEADERS]
+    t = min(os.path.getmtime(lib.out) for lib in LIBS)
+    deps = _headers(True) + [os.path.join(CSRC, f) for lib in LIBS for f in lib.sources + lib.deps]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
 def build(force: bool = False, verbose: bool = True) -> str:
-    """One object per source (compiled in parallel, rebuilt only when the source or a header is newer), then one link."""
+    """One object per source (compiled in parallel, rebuilt only when the source or a header is newer), then one link per library."""
     if not (force or _stale()):
         return OUT
     from concurrent.futures import ThreadPoolExecutor
     hipcc = os.environ.get("HIPCC", "hipcc")
     extra = os.environ.get("ORBX_EXTRA_FLAGS", "").split()
-    objdir = os.path.join(HERE, "build") if OUT.endswith("/liborbx.so") else OUT + ".obj"
+    objdir = os.path.join(HERE, "build") if OUT == os.path.join(HERE, "liborbx.so") else OUT + ".obj"   # an experiment build keeps its objects beside it
     os.makedirs(objdir, exist_ok=True)
     cflags = [f for f in FLAGS if f not in ("-shared", "-ldl")] + extra
-    headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if not f.endswith(".hip") or f == "orbx_kernels.hip"] + \
-              [os.path.join(HERE, "..", "include", h) for h in HEADERS]
-    hnew = max(os.path.getmtime(h) for h in headers if os.path.isfile(h))
     tag = os.path.join(objdir, ".flags")
     flags_now = " ".join([hipcc] + cflags)
     same_flags = os.path.exists(tag) and open(tag).read() == flags_now
 
-    def compile_one(src):
-        obj = os.path.join(objdir, os.path.basename(src).replace(".hip", ".o"))
-        sp = os.path.join(CSRC, src)
-        newest = max(os.path.getmtime(sp), hnew)
-        if src == DEBUG_SOURCE:   # it IS the extractor's translation unit
-            newest = max(newest, os.path.getmtime(os.path.join(CSRC, "orbx_extractor.hip")))
-        if not force and same_flags and os.path.exists(obj) and os.path.getmtime(obj) > newest:
-            return obj
-        cmd = [hipcc] + cflags + (["-fvisibility=hidden"] if src in (DEBUG_SOURCE, STEREO_SOURCE, BOW_SOURCE) else []) + ["-c", sp, "-o", obj]
+    def run(cmd):
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd, cwd=CSRC)
+
+    def compile_one(job):
+        lib, src = job
+        obj = os.path.join(objdir, os.path.basename(src).replace(".hip", ".o"))
+        made_from = [os.path.join(CSRC, f) for f in (src,) + lib.deps] + _headers(os.path.dirname(src) != "")
+        if force or not same_flags or not os.path.exists(obj) or os.path.getmtime(obj) <= max(os.path.getmtime(f) for f in made_from):
+            run([hipcc] + cflags + (["-fvisibility=hidden"] if lib.hidden else []) + ["-c", os.path.join(CSRC, src), "-o", obj])
         return obj
 
+    jobs = [(lib, src) for lib in LIBS for src in lib.sources]
     with ThreadPoolExecutor(max_workers=len(SOURCES) + 1) as ex:
-        objs = list(ex.map(compile_one, SOURCES + [DEBUG_SOURCE, TRAIN_SOURCE, STEREO_SOURCE, BOW_SOURCE]))
+        objs = dict(zip(jobs, ex.map(compile_one, jobs)))
     open(tag, "w").write(flags_now)
-    # the debug library is the extractor's translation unit alone: what that unit takes from the others (the vocabulary's device view, ...) it takes
-    # from liborbx.so at load time ($ORIGIN)
-    # (so do the training, the stereo and the bag-of-words library)
     against_product = ["-L", os.path.dirname(OUT), "-l:" + os.path.basename(OUT), "-Wl,-rpath,$ORIGIN"]
-    for out, oo, more in ((OUT, objs[:-4], []), (DEBUG_OUT, objs[-4:-3], against_product), (TRAIN_OUT, objs[-3:-2], against_product),
-                          (STEREO_OUT, objs[-2:-1], against_product), (BOW_OUT, objs[-1:], against_product)):
-        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + oo + more + ["-ldl"]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.check_call(cmd, cwd=CSRC)
+    for lib in LIBS:
+        run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib.out] + [objs[lib, src] for src in lib.sources] +
+            (against_product if lib.product else []) + ["-ldl"])
     return OUT
 
 

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../orbx_internal.h"
+#include "../side/orbx_handle.h"
 #include "../../../include/orbx_bow.h"
 
 namespace {
@@ -245,46 +246,19 @@ __global__ __launch_bounds__(256) void k_bowb_score(BowbSide q, BowbSide db, int
                                         : bowb_merge(q.ids + qs, q.vals + qs, qn, db.ids + ds, db.vals + ds, dn);
 }
 
-thread_local std::string t_create_err;
-
 }  // namespace
 
-struct orbx_bow {
+struct orbx_bow : orbx::side::Handle {    // scratch: records [slots] + keys [2][slots]
   orbx_voc* voc = nullptr;
-  int levelsup = 0, device = 0;
+  int levelsup = 0;
   int accumulate = 0, norm = kNormNone;   // learnt from orbx_bow_finalize at create
   int lds_limit = kBowLds;                // ORBX_BOW_LDS at create
-  hipStream_t st = nullptr;
-  hipEvent_t ev_done = nullptr;
-  bool pending = false;                   // ev_done recorded: the previous call's work may still use the scratch
-  uint8_t* d_scratch = nullptr; size_t scratch_slots = 0;   // records [slots] + keys [2][slots]
-  uint8_t* d_io = nullptr; size_t io_bytes = 0;             // the host forms' device copies
-  std::vector<uint8_t> h_io;                                // the host forms' fixed-stride results before compaction
-  std::string err;
+  std::vector<uint8_t> h_io;              // the host forms' fixed-stride results before compaction
 };
 
 namespace {
 
-int fail(orbx_bow* b, int code, const std::string& msg) {
-  b->err = msg;
-  return code;
-}
-
-#define BB_HIP(b, expr)                                                                                        \
-  do {                                                                                                         \
-    const hipError_t e_ = (expr);                                                                              \
-    if (e_ != hipSuccess) {                                                                                    \
-      (void)hipGetLastError();                                                                                 \
-      return fail(b, ORBX_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));                        \
-    }                                                                                                          \
-  } while (0)
-
-// the device a pointer lives on, -1 when the runtime does not know it (then nothing is concluded from it)
-int pointer_device(const void* p) {
-  hipPointerAttribute_t at;
-  if (!p || hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return -1; }
-  return at.type == hipMemoryTypeDevice ? at.device : -1;
-}
+using namespace orbx::side;
 
 struct Scratch { uint32_t* word; double* weight; uint32_t* node; u64* keys; };
 size_t scratch_layout(size_t slots, Scratch* s, uint8_t* base) {
@@ -294,32 +268,13 @@ size_t scratch_layout(size_t slots, Scratch* s, uint8_t* base) {
   return l.size;
 }
 
-// the handle's previous work is over and its stream idle: a buffer of the handle may be replaced
-int quiesce(orbx_bow* b) {
-  if (b->pending) BB_HIP(b, hipEventSynchronize(b->ev_done));
-  b->pending = false;
-  BB_HIP(b, hipStreamSynchronize(b->st));
-  return ORBX_OK;
-}
-
-int grow_io(orbx_bow* b, size_t bytes) {
-  if (bytes <= b->io_bytes) return ORBX_OK;
-  const int rc = quiesce(b);
-  if (rc != ORBX_OK) return rc;
-  if (b->d_io) (void)hipFree(b->d_io);
-  b->d_io = nullptr; b->io_bytes = 0;
-  BB_HIP(b, hipMalloc((void**)&b->d_io, bytes));
-  b->io_bytes = bytes;
-  return ORBX_OK;
-}
-
 }  // namespace
 
 extern "C" {
 
 int orbx_bow_create(orbx_bow** out, orbx_voc* voc, int levelsup) {
   if (out) *out = nullptr;
-  auto bad = [](const char* m) { t_create_err = std::string("orbx_bow_create: ") + m; return ORBX_E_INVALID; };
+  auto bad = [](const char* m, int code = ORBX_E_INVALID) { return create_fail(code, "orbx_bow_create", m); };
   if (!out || !voc) return bad("null argument");
   if (levelsup < 0) return bad("levelsup must be >= 0");
   int nnodes = 0;
@@ -340,33 +295,21 @@ int orbx_bow_create(orbx_bow** out, orbx_voc* voc, int levelsup) {
   if (added) norm = vals[0] == 0.5 ? kNormL1 : vals[0] == 1.0 ? kNormCount : kNormL2;
   else norm = vals[0] == 1.0 ? kNormNone : vals[0] == 1.0 / 3.0 ? kNormL1 : kNormL2;
   if (norm == kNormL2 && vals[0] != (added ? 2.0 / std::sqrt(8.0) : 1.0 / std::sqrt(5.0))) return bad("orbx_bow_finalize gave an unknown normalisation on the probe");
-  if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); t_create_err = "orbx_bow_create: hipSetDevice failed"; return ORBX_E_DEVICE; }
   orbx_bow* b = new orbx_bow();
-  b->voc = voc; b->levelsup = levelsup; b->device = device; b->accumulate = added ? 1 : 0; b->norm = norm;
+  b->voc = voc; b->levelsup = levelsup; b->accumulate = added ? 1 : 0; b->norm = norm;
   if (const char* e = std::getenv("ORBX_BOW_LDS")) b->lds_limit = std::max(0, std::min(kBowLds, std::atoi(e)));
-  if (hipStreamCreateWithFlags(&b->st, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&b->ev_done, hipEventDisableTiming) != hipSuccess) {
-    (void)hipGetLastError();
-    orbx_bow_destroy(b);
-    t_create_err = "orbx_bow_create: stream / event creation failed";
-    return ORBX_E_DEVICE;
-  }
+  if (const char* e = open_handle(b, device)) { orbx_bow_destroy(b); return bad(e, ORBX_E_DEVICE); }
   *out = b;
   return ORBX_OK;
 }
 
 void orbx_bow_destroy(orbx_bow* b) {
   if (!b) return;
-  (void)hipSetDevice(b->device);
-  if (b->pending && b->ev_done) (void)hipEventSynchronize(b->ev_done);
-  if (b->st) (void)hipStreamSynchronize(b->st);
-  if (b->d_scratch) (void)hipFree(b->d_scratch);
-  if (b->d_io) (void)hipFree(b->d_io);
-  if (b->ev_done) (void)hipEventDestroy(b->ev_done);
-  if (b->st) (void)hipStreamDestroy(b->st);
+  close_handle(b);
   delete b;
 }
 
-const char* orbx_bow_last_error(const orbx_bow* b) { return b ? b->err.c_str() : t_create_err.c_str(); }
+const char* orbx_bow_last_error(const orbx_bow* b) { return last_error(b); }
 
 int orbx_bow_transform_batch_device(orbx_bow* b, const uint8_t* d_desc, const int32_t* d_counts, int nframes, int capacity, uint32_t* d_bow_ids,
                                     double* d_bow_vals, int32_t* d_bow_n, uint32_t* d_fv_node, int32_t* d_fv_ptr, uint32_t* d_fv_feat,
@@ -386,21 +329,15 @@ int orbx_bow_transform_batch_device(orbx_bow* b, const uint8_t* d_desc, const in
     if (pd >= 0 && pd != b->device)
       return fail(b, ORBX_E_INVALID, std::string(who) + "a buffer lives on device " + std::to_string(pd) + ", the vocabulary on device " + std::to_string(b->device));
   }
-  BB_HIP(b, hipSetDevice(b->device));
+  ORBX_SIDE_HIP(b, hipSetDevice(b->device));
   const size_t slots = (size_t)nframes * capacity;
-  if (slots > b->scratch_slots) {
-    const int rc = quiesce(b);           // the previous call may still use the old scratch
-    if (rc != ORBX_OK) return rc;
-    if (b->d_scratch) (void)hipFree(b->d_scratch);
-    b->d_scratch = nullptr; b->scratch_slots = 0;
-    BB_HIP(b, hipMalloc((void**)&b->d_scratch, scratch_layout(slots, nullptr, nullptr)));
-    b->scratch_slots = slots;
-  }
+  int rc = grow(b, &b->scratch, scratch_layout(slots, nullptr, nullptr));
+  if (rc != ORBX_OK) return rc;
   Scratch sc;
-  scratch_layout(b->scratch_slots, &sc, b->d_scratch);
+  scratch_layout(slots, &sc, b->scratch.p);
   hipStream_t st = stream ? (hipStream_t)stream : b->st;
-  if (b->pending) BB_HIP(b, hipStreamWaitEvent(st, b->ev_done, 0));   // calls on one handle share its scratch: one after the other
-  const int rc = orbx_bow_transform_device(b->voc, d_desc, (int)slots, b->levelsup, sc.word, sc.weight, sc.node, st);
+  if ((rc = wait_previous(b, st)) != ORBX_OK) return rc;
+  rc = orbx_bow_transform_device(b->voc, d_desc, (int)slots, b->levelsup, sc.word, sc.weight, sc.node, st);
   if (rc != ORBX_OK) return fail(b, rc, std::string(who) + "the descent failed");
   BowbArgs a;
   a.word = sc.word; a.weight = sc.weight; a.node = sc.node; a.counts = d_counts; a.gkeys = sc.keys;
@@ -408,10 +345,7 @@ int orbx_bow_transform_batch_device(orbx_bow* b, const uint8_t* d_desc, const in
   a.fv_node = d_fv_node; a.fv_ptr = d_fv_ptr; a.fv_feat = d_fv_feat; a.fv_n = d_fv_n;
   a.cap = capacity; a.lds_limit = b->lds_limit; a.accumulate = b->accumulate; a.norm = b->norm; a.part0 = nb ? 0 : 1;
   hipLaunchKernelGGL(k_bowb_frame, dim3((unsigned)nframes, (nb && nf) ? 2u : 1u), dim3(kBowThreads), 0, st, a);
-  BB_HIP(b, hipGetLastError());
-  BB_HIP(b, hipEventRecord(b->ev_done, st));
-  b->pending = true;
-  return ORBX_OK;
+  return record_call(b, st);
 }
 
 int orbx_bow_transform_batch(orbx_bow* b, const uint8_t* desc, const int32_t* counts, int nframes, int capacity, int32_t* bow_ptr, uint32_t* bow_ids,
@@ -428,22 +362,21 @@ int orbx_bow_transform_batch(orbx_bow* b, const uint8_t* desc, const int32_t* co
   const size_t o_out = io.size;          // the results, read back in one copy
   const size_t o_bv = io.add(nk * 8), o_bi = io.add(nk * 4), o_bn = io.add(nfr * 4), o_fn = io.add(nk * 4), o_fp = io.add((nk + nfr) * 4),
                o_ff = io.add(nk * 4), o_fc = io.add(nfr * 4);
-  BB_HIP(b, hipSetDevice(b->device));
-  int rc = grow_io(b, io.size);
+  ORBX_SIDE_HIP(b, hipSetDevice(b->device));
+  int rc = grow(b, &b->io, io.size);
   if (rc != ORBX_OK) return rc;
   if (b->h_io.size() < io.size - o_out) b->h_io.resize(io.size - o_out);
-  uint8_t* d = b->d_io;
+  uint8_t* d = b->io.p;
   hipStream_t st = b->st;
-  BB_HIP(b, hipMemcpyAsync(d + o_desc, desc, nk * 32, hipMemcpyHostToDevice, st));
-  BB_HIP(b, hipMemcpyAsync(d + o_cnt, counts, nfr * 8, hipMemcpyHostToDevice, st));
+  ORBX_SIDE_HIP(b, hipMemcpyAsync(d + o_desc, desc, nk * 32, hipMemcpyHostToDevice, st));
+  ORBX_SIDE_HIP(b, hipMemcpyAsync(d + o_cnt, counts, nfr * 8, hipMemcpyHostToDevice, st));
   rc = orbx_bow_transform_batch_device(b, d + o_desc, (const int32_t*)(d + o_cnt), nframes, capacity, (uint32_t*)(d + o_bi), (double*)(d + o_bv),
                                        (int32_t*)(d + o_bn), (uint32_t*)(d + o_fn), (int32_t*)(d + o_fp), (uint32_t*)(d + o_ff),
                                        (int32_t*)(d + o_fc), st);
   if (rc != ORBX_OK) return rc;
   uint8_t* h = b->h_io.data();
-  BB_HIP(b, hipMemcpyAsync(h, d + o_out, io.size - o_out, hipMemcpyDeviceToHost, st));
-  BB_HIP(b, hipStreamSynchronize(st));
-  b->pending = false;
+  ORBX_SIDE_HIP(b, hipMemcpyAsync(h, d + o_out, io.size - o_out, hipMemcpyDeviceToHost, st));
+  if ((rc = finish_host(b)) != ORBX_OK) return rc;
   const double* hbv = (const double*)(h + o_bv - o_out);
   const uint32_t* hbi = (const uint32_t*)(h + o_bi - o_out);
   const int32_t* hbn = (const int32_t*)(h + o_bn - o_out);
@@ -483,15 +416,13 @@ int orbx_bow_score_matrix_device(orbx_bow* b, const uint32_t* d_q_ids, const dou
     if (pd >= 0 && pd != b->device)
       return fail(b, ORBX_E_INVALID, std::string(who) + "a buffer lives on device " + std::to_string(pd) + ", the vocabulary on device " + std::to_string(b->device));
   }
-  BB_HIP(b, hipSetDevice(b->device));
+  ORBX_SIDE_HIP(b, hipSetDevice(b->device));
   hipStream_t st = stream ? (hipStream_t)stream : b->st;
-  if (b->pending) BB_HIP(b, hipStreamWaitEvent(st, b->ev_done, 0));
+  const int rc = wait_previous(b, st);
+  if (rc != ORBX_OK) return rc;
   const BowbSide q = {d_q_ids, d_q_vals, d_q_n, nullptr, q_stride}, db = {d_db_ids, d_db_vals, d_db_n, nullptr, db_stride};
   hipLaunchKernelGGL(k_bowb_score, dim3((unsigned)((ndb + 255) / 256), (unsigned)nq), dim3(256), 0, st, q, db, ndb, d_scores);
-  BB_HIP(b, hipGetLastError());
-  BB_HIP(b, hipEventRecord(b->ev_done, st));
-  b->pending = true;
-  return ORBX_OK;
+  return record_call(b, st);
 }
 
 int orbx_bow_score_matrix(orbx_bow* b, const int32_t* q_ptr, const uint32_t* q_ids, const double* q_vals, int nq, const int32_t* db_ptr,
@@ -506,24 +437,22 @@ int orbx_bow_score_matrix(orbx_bow* b, const int32_t* q_ptr, const uint32_t* q_i
   orbx::BlobLayout io;
   const size_t o_qv = io.add(qz * 8), o_dv = io.add(dz * 8), o_s = io.add((size_t)nq * ndb * 8), o_qi = io.add(qz * 4), o_di = io.add(dz * 4),
                o_qp = io.add(((size_t)nq + 1) * 4), o_dp = io.add(((size_t)ndb + 1) * 4);
-  BB_HIP(b, hipSetDevice(b->device));
-  const int rc = grow_io(b, io.size);
+  ORBX_SIDE_HIP(b, hipSetDevice(b->device));
+  int rc = grow(b, &b->io, io.size);
   if (rc != ORBX_OK) return rc;
-  uint8_t* d = b->d_io;
+  uint8_t* d = b->io.p;
   hipStream_t st = b->st;
-  if (b->pending) BB_HIP(b, hipStreamWaitEvent(st, b->ev_done, 0));
-  if (qz) { BB_HIP(b, hipMemcpyAsync(d + o_qi, q_ids, qz * 4, hipMemcpyHostToDevice, st)); BB_HIP(b, hipMemcpyAsync(d + o_qv, q_vals, qz * 8, hipMemcpyHostToDevice, st)); }
-  if (dz) { BB_HIP(b, hipMemcpyAsync(d + o_di, db_ids, dz * 4, hipMemcpyHostToDevice, st)); BB_HIP(b, hipMemcpyAsync(d + o_dv, db_vals, dz * 8, hipMemcpyHostToDevice, st)); }
-  BB_HIP(b, hipMemcpyAsync(d + o_qp, q_ptr, ((size_t)nq + 1) * 4, hipMemcpyHostToDevice, st));
-  BB_HIP(b, hipMemcpyAsync(d + o_dp, db_ptr, ((size_t)ndb + 1) * 4, hipMemcpyHostToDevice, st));
+  if ((rc = wait_previous(b, st)) != ORBX_OK) return rc;
+  if (qz) { ORBX_SIDE_HIP(b, hipMemcpyAsync(d + o_qi, q_ids, qz * 4, hipMemcpyHostToDevice, st)); ORBX_SIDE_HIP(b, hipMemcpyAsync(d + o_qv, q_vals, qz * 8, hipMemcpyHostToDevice, st)); }
+  if (dz) { ORBX_SIDE_HIP(b, hipMemcpyAsync(d + o_di, db_ids, dz * 4, hipMemcpyHostToDevice, st)); ORBX_SIDE_HIP(b, hipMemcpyAsync(d + o_dv, db_vals, dz * 8, hipMemcpyHostToDevice, st)); }
+  ORBX_SIDE_HIP(b, hipMemcpyAsync(d + o_qp, q_ptr, ((size_t)nq + 1) * 4, hipMemcpyHostToDevice, st));
+  ORBX_SIDE_HIP(b, hipMemcpyAsync(d + o_dp, db_ptr, ((size_t)ndb + 1) * 4, hipMemcpyHostToDevice, st));
   const BowbSide q = {(const uint32_t*)(d + o_qi), (const double*)(d + o_qv), nullptr, (const int32_t*)(d + o_qp), 0},
                  db = {(const uint32_t*)(d + o_di), (const double*)(d + o_dv), nullptr, (const int32_t*)(d + o_dp), 0};
   hipLaunchKernelGGL(k_bowb_score, dim3((unsigned)((ndb + 255) / 256), (unsigned)nq), dim3(256), 0, st, q, db, ndb, (double*)(d + o_s));
-  BB_HIP(b, hipGetLastError());
-  BB_HIP(b, hipMemcpyAsync(scores, d + o_s, (size_t)nq * ndb * 8, hipMemcpyDeviceToHost, st));
-  BB_HIP(b, hipStreamSynchronize(st));
-  b->pending = false;
-  return ORBX_OK;
+  ORBX_SIDE_HIP(b, hipGetLastError());
+  ORBX_SIDE_HIP(b, hipMemcpyAsync(scores, d + o_s, (size_t)nq * ndb * 8, hipMemcpyDeviceToHost, st));
+  return finish_host(b);
 }
 
 }  // extern "C"

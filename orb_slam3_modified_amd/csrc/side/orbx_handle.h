@@ -1,0 +1,116 @@
+// The host-side core of a side library's handle (liborbx_stereo.so, liborbx_bow.so: DESIGN.md sections 10 and 11).  Host code only; it sits
+// below csrc/, outside kernels_hash().  A handle derives from orbx::side::Handle and adds what is its own.
+//
+// The rule it keeps: the calls on one handle share its scratch, so each waits for the one before it (wait_previous / record_call around
+// ev_done), and a block of the handle is replaced only once the handle is idle (grow behind quiesce).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "../../../include/orbx.h"
+
+namespace orbx {
+namespace side {
+
+struct Block { uint8_t* p = nullptr; size_t bytes = 0; };   // a grow-only device allocation
+
+struct Handle {
+  int device = 0;
+  hipStream_t st = nullptr;        // the host forms' copies and kernels; a device form without a stream argument
+  hipEvent_t ev_done = nullptr;
+  bool pending = false;            // ev_done recorded: the previous call's work may still use the scratch
+  Block scratch;                   // the kernels' intermediate buffers
+  Block io;                        // the host forms' device copies of arguments and results
+  std::string err;
+};
+
+inline thread_local std::string t_create_err;   // why the last create of this thread failed: there is no handle to hold it
+
+inline int fail(Handle* h, int code, const std::string& msg) {
+  h->err = msg;
+  return code;
+}
+inline int create_fail(int code, const char* who, const char* msg) {
+  t_create_err = std::string(who) + ": " + msg;
+  return code;
+}
+inline const char* last_error(const Handle* h) { return h ? h->err.c_str() : t_create_err.c_str(); }
+
+// returns ORBX_E_DEVICE from the calling function, with the runtime's sticky error cleared
+#define ORBX_SIDE_HIP(h, expr)                                                                                 \
+  do {                                                                                                         \
+    const hipError_t e_ = (expr);                                                                              \
+    if (e_ != hipSuccess) {                                                                                    \
+      (void)hipGetLastError();                                                                                 \
+      return orbx::side::fail((h), ORBX_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));          \
+    }                                                                                                          \
+  } while (0)
+
+// the handle's previous work is over and its stream idle: a block of the handle may be replaced
+inline int quiesce(Handle* h) {
+  if (h->pending) ORBX_SIDE_HIP(h, hipEventSynchronize(h->ev_done));
+  h->pending = false;
+  ORBX_SIDE_HIP(h, hipStreamSynchronize(h->st));
+  return ORBX_OK;
+}
+
+// calls on one handle share its scratch: one after the other
+inline int wait_previous(Handle* h, hipStream_t st) {
+  if (h->pending) ORBX_SIDE_HIP(h, hipStreamWaitEvent(st, h->ev_done, 0));
+  return ORBX_OK;
+}
+// after a call's last launch on `st`: the launches went through, and the next call waits for them
+inline int record_call(Handle* h, hipStream_t st) {
+  ORBX_SIDE_HIP(h, hipGetLastError());
+  ORBX_SIDE_HIP(h, hipEventRecord(h->ev_done, st));
+  h->pending = true;
+  return ORBX_OK;
+}
+// the tail of a host form: everything queued on the handle's stream is done, the results are in the caller's memory
+inline int finish_host(Handle* h) {
+  ORBX_SIDE_HIP(h, hipStreamSynchronize(h->st));
+  h->pending = false;
+  return ORBX_OK;
+}
+
+inline int grow(Handle* h, Block* b, size_t bytes) {
+  if (bytes <= b->bytes) return ORBX_OK;
+  const int rc = quiesce(h);             // the previous call may still use the old block
+  if (rc != ORBX_OK) return rc;
+  if (b->p) (void)hipFree(b->p);
+  b->p = nullptr; b->bytes = 0;
+  ORBX_SIDE_HIP(h, hipMalloc((void**)&b->p, bytes));
+  b->bytes = bytes;
+  return ORBX_OK;
+}
+
+// the device a pointer lives on, -1 when the runtime does not know it (then nothing is concluded from it)
+inline int pointer_device(const void* p) {
+  hipPointerAttribute_t at;
+  if (!p || hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return -1; }
+  return at.type == hipMemoryTypeDevice ? at.device : -1;
+}
+
+// the handle's stream and event on `device`; what failed, or nullptr.  close_handle() takes a half-opened handle too
+inline const char* open_handle(Handle* h, int device) {
+  h->device = device;
+  if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return "hipSetDevice failed"; }
+  if (hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&h->ev_done, hipEventDisableTiming) != hipSuccess) {
+    (void)hipGetLastError();
+    return "stream / event creation failed";
+  }
+  return nullptr;
+}
+inline void close_handle(Handle* h) {
+  (void)hipSetDevice(h->device);
+  if (h->pending && h->ev_done) (void)hipEventSynchronize(h->ev_done);
+  if (h->st) (void)hipStreamSynchronize(h->st);
+  if (h->scratch.p) (void)hipFree(h->scratch.p);
+  if (h->io.p) (void)hipFree(h->io.p);
+  if (h->ev_done) (void)hipEventDestroy(h->ev_done);
+  if (h->st) (void)hipStreamDestroy(h->st);
+}
+
+}  // namespace side
+}  // namespace orbx

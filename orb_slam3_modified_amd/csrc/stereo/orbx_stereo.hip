@@ -20,6 +20,7 @@
 #include <string>
 
 #include "../orbx_internal.h"
+#include "../side/orbx_handle.h"
 #include "../../../include/orbx_stereo.h"
 
 namespace {
@@ -291,39 +292,19 @@ __global__ __launch_bounds__(1024) void k_sb_filter(const int32_t* __restrict__ 
   if (t == 0) kept_out[f] = kept;
 }
 
-thread_local std::string t_create_err;
-
 }  // namespace
 
-struct orbx_stereo {
-  orbx_ctx* left = nullptr;
+struct orbx_stereo : orbx::side::Handle {   // scratch: gates [frames][cap] + SADs [frames][cap]; io: keypoints, descriptors, counts and results
+  orbx_ctx* left = nullptr;                 // (never frames: level 0 of a batch must live in memory its context owns, as it outlives the handle)
   orbx_ctx* right = nullptr;
   float mb = 0.0f, mbf = 0.0f;
-  int device = 0;
-  hipStream_t st = nullptr;        // the copies and the association of the host-buffer form
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_done = nullptr;
-  bool pending = false;            // ev_done recorded: the previous call's work may still use the scratch
-  uint2* d_gates = nullptr;        // [frames][cap]
-  int32_t* d_sad = nullptr;        // [frames][cap]
-  size_t scratch_slots = 0;
-  uint8_t* d_io = nullptr; size_t io_bytes = 0;   // the host-buffer form's device copies of keypoints, descriptors, counts and results (never
-                                                  // frames: level 0 of a batch must live in memory its context owns, as it outlives the handle)
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   int tile = kSbTile, filter_lds = kSbLdsSad;     // ORBX_STEREO_TILE / ORBX_STEREO_FILTER_LDS at create (the tiled and the global-memory paths)
-  std::string err;
 };
 
 namespace {
 
-int fail(orbx_stereo* s, int code, const std::string& msg) {
-  s->err = msg;
-  return code;
-}
-
-#define SB_HIP(s, expr)                                                                             \
-  do {                                                                                              \
-    hipError_t _e = (expr);                                                                         \
-    if (_e != hipSuccess) return fail((s), ORBX_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
+using namespace orbx::side;
 
 // what makes the two extractions of a pair comparable: Frame's stereo constructor builds both extractors from one set of settings
 const char* param_mismatch(const orbx_ctx* a, const orbx_ctx* b) {
@@ -352,45 +333,36 @@ extern "C" {
 
 int orbx_stereo_create(orbx_stereo** out, orbx_ctx* left, orbx_ctx* right, float mb, float mbf) {
   if (out) *out = nullptr;
-  auto bad = [](const char* m) { t_create_err = std::string("orbx_stereo_create: ") + m; return ORBX_E_INVALID; };
+  auto bad = [](const char* m, int code = ORBX_E_INVALID) { return create_fail(code, "orbx_stereo_create", m); };
   if (!out || !left || !right) return bad("null argument");
   if (left == right) return bad("the left and the right side need two contexts");
   if (const char* m = param_mismatch(left, right)) return bad(m);
   if (!(mb > 0)) return bad("mb (the baseline) must be > 0");
   if (!std::isfinite(mbf)) return bad("mbf must be finite");
-  if (hipSetDevice(left->device) != hipSuccess) { (void)hipGetLastError(); t_create_err = "orbx_stereo_create: hipSetDevice failed"; return ORBX_E_DEVICE; }
   orbx_stereo* s = new orbx_stereo();
-  s->left = left; s->right = right; s->mb = mb; s->mbf = mbf; s->device = left->device;
+  s->left = left; s->right = right; s->mb = mb; s->mbf = mbf;
   if (const char* e = std::getenv("ORBX_STEREO_TILE")) s->tile = std::max(1, std::min(kSbTile, std::atoi(e)));
   if (const char* e = std::getenv("ORBX_STEREO_FILTER_LDS")) s->filter_lds = std::max(0, std::min(kSbLdsSad, std::atoi(e)));
-  if (hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&s->ev_done, hipEventDisableTiming) != hipSuccess) {
+  const char* e = open_handle(s, left->device);
+  if (!e && (hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming) != hipSuccess ||
+             hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming) != hipSuccess)) {
     (void)hipGetLastError();
-    orbx_stereo_destroy(s);
-    t_create_err = "orbx_stereo_create: stream / event creation failed";
-    return ORBX_E_DEVICE;
+    e = "stream / event creation failed";
   }
+  if (e) { orbx_stereo_destroy(s); return bad(e, ORBX_E_DEVICE); }
   *out = s;
   return ORBX_OK;
 }
 
 void orbx_stereo_destroy(orbx_stereo* s) {
   if (!s) return;
-  (void)hipSetDevice(s->device);
-  if (s->pending && s->ev_done) (void)hipEventSynchronize(s->ev_done);
-  if (s->st) (void)hipStreamSynchronize(s->st);
-  if (s->d_gates) (void)hipFree(s->d_gates);
-  if (s->d_sad) (void)hipFree(s->d_sad);
-  if (s->d_io) (void)hipFree(s->d_io);
+  close_handle(s);
   if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
   if (s->ev_join) (void)hipEventDestroy(s->ev_join);
-  if (s->ev_done) (void)hipEventDestroy(s->ev_done);
-  if (s->st) (void)hipStreamDestroy(s->st);
   delete s;
 }
 
-const char* orbx_stereo_last_error(const orbx_stereo* s) { return s ? s->err.c_str() : t_create_err.c_str(); }
+const char* orbx_stereo_last_error(const orbx_stereo* s) { return last_error(s); }
 
 int orbx_stereo_match_batch_device(orbx_stereo* s, int nframes, const orbx_keypoint* d_kpsL, const uint8_t* d_descL, const int32_t* d_countsL,
                                    const orbx_keypoint* d_kpsR, const uint8_t* d_descR, const int32_t* d_countsR, float* d_u_right, float* d_depth,
@@ -407,35 +379,28 @@ int orbx_stereo_match_batch_device(orbx_stereo* s, int nframes, const orbx_keypo
   if (!L->d_geo || !R->d_geo || !L->last_imgs || !R->last_imgs || L->geo.rows != R->geo.rows || L->geo.cols != R->geo.cols)
     return fail(s, ORBX_E_INVALID, "orbx_stereo_match_batch_device: the two last batches have different shapes");
   const int cap = L->out_cap;
-  SB_HIP(s, hipSetDevice(s->device));
+  ORBX_SIDE_HIP(s, hipSetDevice(s->device));
   const size_t slots = (size_t)nframes * cap;
-  if (slots > s->scratch_slots) {
-    if (s->pending) SB_HIP(s, hipEventSynchronize(s->ev_done));   // the previous call may still read the old scratch
-    s->pending = false;
-    if (s->d_gates) (void)hipFree(s->d_gates);
-    if (s->d_sad) (void)hipFree(s->d_sad);
-    s->d_gates = nullptr; s->d_sad = nullptr; s->scratch_slots = 0;
-    SB_HIP(s, hipMalloc((void**)&s->d_gates, slots * sizeof(uint2)));
-    SB_HIP(s, hipMalloc((void**)&s->d_sad, slots * sizeof(int32_t)));
-    s->scratch_slots = slots;
-  }
+  orbx::BlobLayout sc;
+  const size_t o_gates = sc.add(slots * sizeof(uint2)), o_sad = sc.add(slots * sizeof(int32_t));
+  int rc = grow(s, &s->scratch, sc.size);
+  if (rc != ORBX_OK) return rc;
+  uint2* d_gates = (uint2*)(s->scratch.p + o_gates);
+  int32_t* d_sad = (int32_t*)(s->scratch.p + o_sad);
   hipStream_t st = stream ? (hipStream_t)stream : L->stream;
-  if (s->pending) SB_HIP(s, hipStreamWaitEvent(st, s->ev_done, 0));   // calls on one handle share its scratch: one after the other
+  if ((rc = wait_previous(s, st)) != ORBX_OK) return rc;
   SbGeom g;
   std::memset(&g, 0, sizeof(g));
   side_geom(L, &g.L);
   side_geom(R, &g.R);
   g.h0 = L->geo.lv[0].h;
   for (int l = 0; l < L->nlevels; l++) { g.w[l] = L->geo.lv[l].w; g.scale[l] = L->scale[l]; g.inv_scale[l] = L->inv_scale[l]; }
-  hipLaunchKernelGGL(k_sb_gates, dim3((unsigned)((cap + 255) / 256), (unsigned)nframes), dim3(256), 0, st, g, d_kpsR, d_countsR, cap, s->d_gates);
+  hipLaunchKernelGGL(k_sb_gates, dim3((unsigned)((cap + 255) / 256), (unsigned)nframes), dim3(256), 0, st, g, d_kpsR, d_countsR, cap, d_gates);
   hipLaunchKernelGGL(k_sb_match, dim3((unsigned)((cap + kSbPerGroup - 1) / kSbPerGroup), (unsigned)nframes), dim3(256), 0, st, g, d_kpsL, d_descL,
-                     d_countsL, d_descR, d_countsR, (const uint2*)s->d_gates, cap, s->tile, s->mb, s->mbf, d_u_right, d_depth, s->d_sad);
+                     d_countsL, d_descR, d_countsR, (const uint2*)d_gates, cap, s->tile, s->mb, s->mbf, d_u_right, d_depth, d_sad);
   hipLaunchKernelGGL(k_sb_filter, dim3((unsigned)nframes), dim3(1024), 0, st, d_countsL, d_countsR, cap, s->filter_lds, d_u_right, d_depth,
-                     (const int32_t*)s->d_sad, d_kept);
-  SB_HIP(s, hipGetLastError());
-  SB_HIP(s, hipEventRecord(s->ev_done, st));
-  s->pending = true;
-  return ORBX_OK;
+                     (const int32_t*)d_sad, d_kept);
+  return record_call(s, st);
 }
 
 int orbx_stereo_extract_batch_device(orbx_stereo* s, const uint8_t* d_imgsL, const uint8_t* d_imgsR, int nframes, int rows, int cols,
@@ -445,20 +410,20 @@ int orbx_stereo_extract_batch_device(orbx_stereo* s, const uint8_t* d_imgsL, con
   if (!s) return ORBX_E_INVALID;
   if (!d_imgsL || !d_imgsR || nframes < 1) return fail(s, ORBX_E_INVALID, "orbx_stereo_extract_batch_device: no frames");
   if (const char* m = param_mismatch(s->left, s->right)) return fail(s, ORBX_E_INVALID, std::string("orbx_stereo_extract_batch_device: ") + m);
-  SB_HIP(s, hipSetDevice(s->device));
+  ORBX_SIDE_HIP(s, hipSetDevice(s->device));
   hipStream_t st = stream ? (hipStream_t)stream : s->left->stream;
   // the right side on the right context's own stream (a NULL stream argument), forked from and joined back into the caller's: the context
   // then remembers no stream of this handle, which may be destroyed before the context
   hipStream_t sr = s->right->stream;
-  SB_HIP(s, hipEventRecord(s->ev_fork, st));
-  SB_HIP(s, hipStreamWaitEvent(sr, s->ev_fork, 0));
+  ORBX_SIDE_HIP(s, hipEventRecord(s->ev_fork, st));
+  ORBX_SIDE_HIP(s, hipStreamWaitEvent(sr, s->ev_fork, 0));
   int rc = orbx_extract_batch_device(s->left, d_imgsL, nframes, rows, cols, row_stride, frame_stride, 0, 0, d_kpsL, d_descL, d_countsL, st);
   if (rc != ORBX_OK) return fail(s, rc, std::string("left extraction: ") + orbx_last_error(s->left));
   rc = orbx_extract_batch_device(s->right, d_imgsR, nframes, rows, cols, row_stride, frame_stride, 0, 0, d_kpsR, d_descR, d_countsR, nullptr);
   const hipError_t e1 = hipEventRecord(s->ev_join, sr), e2 = hipStreamWaitEvent(st, s->ev_join, 0);   // joined whether or not it succeeded
   if (rc != ORBX_OK) return fail(s, rc, std::string("right extraction: ") + orbx_last_error(s->right));
-  SB_HIP(s, e1);
-  SB_HIP(s, e2);
+  ORBX_SIDE_HIP(s, e1);
+  ORBX_SIDE_HIP(s, e2);
   return orbx_stereo_match_batch_device(s, nframes, d_kpsL, d_descL, d_countsL, d_kpsR, d_descR, d_countsR, d_u_right, d_depth, d_kept, st);
 }
 
@@ -482,34 +447,24 @@ int orbx_stereo_extract_batch(orbx_stereo* s, const uint8_t* imgsL, const uint8_
   const size_t o_kL = io.add(nk * sizeof(orbx_keypoint)), o_kR = io.add(nk * sizeof(orbx_keypoint)), o_dL = io.add(nk * 32),
                o_dR = io.add(nk * 32), o_cL = io.add((size_t)nframes * 8), o_cR = io.add((size_t)nframes * 8), o_u = io.add(nk * 4),
                o_d = io.add(nk * 4), o_k = io.add((size_t)nframes * 4);
-  SB_HIP(s, hipSetDevice(s->device));
+  ORBX_SIDE_HIP(s, hipSetDevice(s->device));
   hipStream_t st = s->st;
-  if (io.size > s->io_bytes) {
-    if (s->pending) SB_HIP(s, hipEventSynchronize(s->ev_done));   // a device-form call may still read the old block
-    s->pending = false;
-    SB_HIP(s, hipStreamSynchronize(st));
-    if (s->d_io) (void)hipFree(s->d_io);
-    s->d_io = nullptr; s->io_bytes = 0;
-    SB_HIP(s, hipMalloc((void**)&s->d_io, io.size));
-    s->io_bytes = io.size;
-  }
-  uint8_t* d = s->d_io;
-  SB_HIP(s, hipMemcpyAsync(d + o_kL, kpsL, nk * sizeof(orbx_keypoint), hipMemcpyHostToDevice, st));
-  SB_HIP(s, hipMemcpyAsync(d + o_kR, kpsR, nk * sizeof(orbx_keypoint), hipMemcpyHostToDevice, st));
-  SB_HIP(s, hipMemcpyAsync(d + o_dL, descL, nk * 32, hipMemcpyHostToDevice, st));
-  SB_HIP(s, hipMemcpyAsync(d + o_dR, descR, nk * 32, hipMemcpyHostToDevice, st));
-  SB_HIP(s, hipMemcpyAsync(d + o_cL, countsL, (size_t)nframes * 8, hipMemcpyHostToDevice, st));
-  SB_HIP(s, hipMemcpyAsync(d + o_cR, countsR, (size_t)nframes * 8, hipMemcpyHostToDevice, st));
+  if ((rc = grow(s, &s->io, io.size)) != ORBX_OK) return rc;
+  uint8_t* d = s->io.p;
+  ORBX_SIDE_HIP(s, hipMemcpyAsync(d + o_kL, kpsL, nk * sizeof(orbx_keypoint), hipMemcpyHostToDevice, st));
+  ORBX_SIDE_HIP(s, hipMemcpyAsync(d + o_kR, kpsR, nk * sizeof(orbx_keypoint), hipMemcpyHostToDevice, st));
+  ORBX_SIDE_HIP(s, hipMemcpyAsync(d + o_dL, descL, nk * 32, hipMemcpyHostToDevice, st));
+  ORBX_SIDE_HIP(s, hipMemcpyAsync(d + o_dR, descR, nk * 32, hipMemcpyHostToDevice, st));
+  ORBX_SIDE_HIP(s, hipMemcpyAsync(d + o_cL, countsL, (size_t)nframes * 8, hipMemcpyHostToDevice, st));
+  ORBX_SIDE_HIP(s, hipMemcpyAsync(d + o_cR, countsR, (size_t)nframes * 8, hipMemcpyHostToDevice, st));
   rc = orbx_stereo_match_batch_device(s, nframes, (const orbx_keypoint*)(d + o_kL), d + o_dL, (const int32_t*)(d + o_cL),
                                       (const orbx_keypoint*)(d + o_kR), d + o_dR, (const int32_t*)(d + o_cR), (float*)(d + o_u), (float*)(d + o_d),
                                       (int32_t*)(d + o_k), st);
   if (rc != ORBX_OK) return rc;
-  SB_HIP(s, hipMemcpyAsync(u_right, d + o_u, nk * 4, hipMemcpyDeviceToHost, st));
-  SB_HIP(s, hipMemcpyAsync(depth, d + o_d, nk * 4, hipMemcpyDeviceToHost, st));
-  SB_HIP(s, hipMemcpyAsync(kept, d + o_k, (size_t)nframes * 4, hipMemcpyDeviceToHost, st));
-  SB_HIP(s, hipStreamSynchronize(st));
-  s->pending = false;
-  return ORBX_OK;
+  ORBX_SIDE_HIP(s, hipMemcpyAsync(u_right, d + o_u, nk * 4, hipMemcpyDeviceToHost, st));
+  ORBX_SIDE_HIP(s, hipMemcpyAsync(depth, d + o_d, nk * 4, hipMemcpyDeviceToHost, st));
+  ORBX_SIDE_HIP(s, hipMemcpyAsync(kept, d + o_k, (size_t)nframes * 4, hipMemcpyDeviceToHost, st));
+  return finish_host(s);
 }
 
 }  // extern "C"

@@ -3,7 +3,6 @@ rectified pairs at once, on the pyramids two extractors left resident, and both 
 All arithmetic runs in the HIP kernels of the library; this file only marshals buffers."""
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 from typing import Tuple
 
@@ -34,35 +33,14 @@ class StereoResult:
                 int(self.kept[f]))
 
 
-class StereoBatch:
+class StereoBatch(_lib.SideHandle):
     """A rectified rig of two ORBextractor instances with identical parameters on one device; mb = baseline, mbf = baseline * fx."""
 
     def __init__(self, left_ex, right_ex, mb: float, mbf: float):
         self._S = _lib.stereo_lib()
-        self._h = C.c_void_p(0)
-        rc = self._S.orbx_stereo_create(C.byref(self._h), left_ex._ctx, right_ex._ctx, float(mb), float(mbf))
-        if rc != 0:
-            m = self._S.orbx_stereo_last_error(None)
-            raise _lib.OrbxError(rc, m.decode() if m else "")
+        super().__init__(self._S, "orbx_stereo", left_ex._ctx, right_ex._ctx, float(mb), float(mbf))
         self.left, self.right, self.mb, self.mbf = left_ex, right_ex, float(mb), float(mbf)
         self.capacity = left_ex.capacity
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._S.orbx_stereo_destroy(self._h)
-            self._h = C.c_void_p(0)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc: int) -> int:
-        if rc < 0:
-            m = self._S.orbx_stereo_last_error(self._h)
-            raise _lib.OrbxError(rc, m.decode() if m else "")
-        return rc
 
     def extract(self, imgsL: np.ndarray, imgsR: np.ndarray) -> StereoResult:
         """Host frames [B, rows, cols] uint8 per side (same shape): both extractions (lapping (0, 0)) and the association."""

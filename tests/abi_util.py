@@ -1,0 +1,53 @@
+"""What the ABI and kernel-resource tests of every library share: the names a header declares, the names a library exports, and one
+source's gfx950 device assembly (hipcc cross-compiles: no GPU needed) with its kernels' private segment sizes."""
+from __future__ import annotations
+
+import functools
+import os
+import re
+import shutil
+import subprocess
+import tempfile
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+needs_hipcc = pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not installed")
+
+
+def declared(header: str = "orbx.h") -> list:
+    """The orbx_* functions include/<header> declares, sorted."""
+    h = open(os.path.join(ROOT, "include", header)).read()
+    h = re.sub(r"/\*.*?\*/", "", h, flags=re.S)
+    return sorted(set(re.findall(r"\b(orbx_[a-z0-9_]+)\s*\(", h)))
+
+
+def exported(path: str) -> set:
+    """The functions a shared library defines and exports."""
+    out = subprocess.check_output(["nm", "-D", "--defined-only", path]).decode()
+    return {l.split()[-1] for l in out.splitlines() if " T " in l}
+
+
+@functools.lru_cache(maxsize=None)
+def device_asm(source: str, hidden: bool = False) -> str:
+    """The device assembly of csrc/<source> under the build's own flags (-fvisibility=hidden as its library is built)."""
+    from orb_slam3_modified_amd.build import CSRC, FLAGS
+    flags = [f for f in FLAGS if f not in ("-shared", "-fPIC", "-ldl")] + (["-fvisibility=hidden"] if hidden else [])
+    tmp = tempfile.mkdtemp(prefix="orbx_asm_")
+    try:
+        out = os.path.join(tmp, "device.s")
+        p = subprocess.run(["hipcc"] + flags + ["-S", "--cuda-device-only", "-o", out, os.path.join(CSRC, source)],
+                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        assert p.returncode == 0, p.stdout[-2000:]
+        return open(out).read()
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
+def kernel_scratch(source: str, hidden: bool = False) -> dict:
+    """kernel symbol -> .amdhsa_private_segment_fixed_size (scratch bytes per work-item) for every kernel of csrc/<source>."""
+    asm = device_asm(source, hidden)
+    kernels = re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", asm, flags=re.M)
+    sizes = re.findall(r"^\s*\.amdhsa_private_segment_fixed_size\s+(\d+)", asm, flags=re.M)
+    assert len(kernels) == len(sizes) == len(set(kernels)), (source, len(kernels), len(sizes))
+    return dict(zip(kernels, map(int, sizes)))

@@ -5,13 +5,9 @@ import re
 
 import pytest
 
+from tests.abi_util import declared as _declared, exported as _exported
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _declared(header="orbx.h"):
-    h = open(os.path.join(ROOT, "include", header)).read()
-    h = re.sub(r"/\*.*?\*/", "", h, flags=re.S)
-    return sorted(set(re.findall(r"\b(orbx_[a-z0-9_]+)\s*\(", h)))
 
 
 def test_library_built_in_tree():
@@ -42,7 +38,7 @@ def test_the_diagnostic_abi_is_a_library_of_its_own():
     assert not [n for n in dnames if not hasattr(D, n)]
     assert not [n for n in dnames if hasattr(P, n)], "liborbx.so exports a debug entry point"
     assert set(_lib.lib()._orbx_debug_symbols) == set(dnames)
-    exported = {l.split()[-1] for l in subprocess.check_output(["nm", "-D", "--defined-only", _lib.DEBUG_LIB_PATH]).decode().splitlines() if " T " in l}
+    exported = _exported(_lib.DEBUG_LIB_PATH)
     assert {e for e in exported if e.startswith("orbx_")} == set(dnames), sorted(e for e in exported if e.startswith("orbx_") and e not in dnames)[:5]
     pexp = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
     assert "k_debug_" not in pexp and "k_calib_copy" not in pexp                 # nor a debug kernel

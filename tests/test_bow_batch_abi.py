@@ -1,26 +1,12 @@
 """include/orbx_bow.h <-> liborbx_bow.so: the batched bag of words is a library of its own beside the product (CPU-only checks)."""
 import ctypes as C
 import os
-import re
-import shutil
-import subprocess
-import tempfile
 
-import pytest
+from tests import abi_util
+from tests.abi_util import declared as _declared, exported as _exported
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ROOT = abi_util.ROOT
 KERNELS_HASH = "eee3be0e614ece87"   # the product's kernel sources: this library changes none of them
-
-
-def _declared(header):
-    h = open(os.path.join(ROOT, "include", header)).read()
-    h = re.sub(r"/\*.*?\*/", "", h, flags=re.S)
-    return sorted(set(re.findall(r"\b(orbx_[a-z0-9_]+)\s*\(", h)))
-
-
-def _exported(path):
-    out = subprocess.check_output(["nm", "-D", "--defined-only", path]).decode()
-    return {l.split()[-1] for l in out.splitlines() if " T " in l}
 
 
 def test_build_produces_the_bow_library():
@@ -75,28 +61,11 @@ def test_create_rejects_bad_arguments_without_a_device():
     B.orbx_bow_destroy(None)
 
 
-@pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not installed")
+@abi_util.needs_hipcc
 def test_bow_kernels_compile_without_scratch():
-    from orb_slam3_modified_amd.build import BOW_SOURCE, CSRC, FLAGS
-    flags = [f for f in FLAGS if f not in ("-shared", "-fPIC", "-ldl")] + ["-fvisibility=hidden"]
-    tmp = tempfile.mkdtemp(prefix="orbx_bow_asm_")
-    out = os.path.join(tmp, "bow.s")
-    try:
-        p = subprocess.run(["hipcc"] + flags + ["-S", "--cuda-device-only", "-o", out, os.path.join(CSRC, BOW_SOURCE)],
-                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert p.returncode == 0, p.stdout[-2000:]
-        scratch = {}
-        name = None
-        for line in open(out):
-            m = re.match(r"\s*\.amdhsa_kernel\s+(\S+)", line)
-            if m:
-                name = m.group(1)
-            m = re.match(r"\s*\.amdhsa_private_segment_fixed_size\s+(\d+)", line)
-            if m:
-                scratch[name] = int(m.group(1))
-        for k in ("k_bowb_frame", "k_bowb_score"):
-            hit = [n for n in scratch if k in n]
-            assert len(hit) == 1, (k, sorted(scratch))
-        assert all(v == 0 for v in scratch.values()), scratch
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
+    from orb_slam3_modified_amd.build import BOW_SOURCE
+    scratch = abi_util.kernel_scratch(BOW_SOURCE, hidden=True)
+    for k in ("k_bowb_frame", "k_bowb_score"):
+        hit = [n for n in scratch if k in n]
+        assert len(hit) == 1, (k, sorted(scratch))
+    assert all(v == 0 for v in scratch.values()), scratch

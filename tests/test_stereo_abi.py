@@ -1,25 +1,11 @@
 """include/orbx_stereo.h <-> liborbx_stereo.so: the batched stereo front-end is a library of its own beside the product (CPU-only checks)."""
 import ctypes as C
 import os
-import re
-import shutil
-import subprocess
-import tempfile
 
-import pytest
+from tests import abi_util
+from tests.abi_util import declared as _declared, exported as _exported
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _declared(header):
-    h = open(os.path.join(ROOT, "include", header)).read()
-    h = re.sub(r"/\*.*?\*/", "", h, flags=re.S)
-    return sorted(set(re.findall(r"\b(orbx_[a-z0-9_]+)\s*\(", h)))
-
-
-def _exported(path):
-    out = subprocess.check_output(["nm", "-D", "--defined-only", path]).decode()
-    return {l.split()[-1] for l in out.splitlines() if " T " in l}
+ROOT = abi_util.ROOT
 
 
 def test_build_produces_the_stereo_library():
@@ -68,31 +54,14 @@ def test_create_rejects_bad_rigs_without_a_device():
     assert S.orbx_stereo_match_batch_device(None, 1, *([None] * 10)) == _lib.ORBX_E_INVALID
 
 
-@pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not installed")
+@abi_util.needs_hipcc
 def test_stereo_kernels_compile_without_scratch():
-    from orb_slam3_modified_amd.build import CSRC, FLAGS, STEREO_SOURCE
-    flags = [f for f in FLAGS if f not in ("-shared", "-fPIC", "-ldl")] + ["-fvisibility=hidden"]
-    tmp = tempfile.mkdtemp(prefix="orbx_stereo_asm_")
-    out = os.path.join(tmp, "stereo.s")
-    try:
-        p = subprocess.run(["hipcc"] + flags + ["-S", "--cuda-device-only", "-o", out, os.path.join(CSRC, STEREO_SOURCE)],
-                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert p.returncode == 0, p.stdout[-2000:]
-        scratch = {}
-        name = None
-        for line in open(out):
-            m = re.match(r"\s*\.amdhsa_kernel\s+(\S+)", line)
-            if m:
-                name = m.group(1)
-            m = re.match(r"\s*\.amdhsa_private_segment_fixed_size\s+(\d+)", line)
-            if m:
-                scratch[name] = int(m.group(1))
-        for k in ("k_sb_gates", "k_sb_match", "k_sb_filter"):
-            hit = [n for n in scratch if k in n]
-            assert len(hit) == 1, (k, sorted(scratch))
-        assert all(v == 0 for v in scratch.values()), scratch
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
+    from orb_slam3_modified_amd.build import STEREO_SOURCE
+    scratch = abi_util.kernel_scratch(STEREO_SOURCE, hidden=True)
+    for k in ("k_sb_gates", "k_sb_match", "k_sb_filter"):
+        hit = [n for n in scratch if k in n]
+        assert len(hit) == 1, (k, sorted(scratch))
+    assert all(v == 0 for v in scratch.values()), scratch
 
 
 def test_stereo_source_is_outside_the_counter_stamp():

@@ -3,16 +3,14 @@ maker, and the zero-scratch rule for the training library's kernels."""
 import ctypes
 import hashlib
 import os
-import re
 import shutil
 import subprocess
 import sys
-import tempfile
 
 import numpy as np
 import pytest
 
-from tests import voc_train_model as M
+from tests import abi_util, voc_train_model as M
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "voc_train.npz")
@@ -83,19 +81,10 @@ def test_golden_maker_reproduces_the_committed_golden():
     subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "make_voc_train_golden.py"), "--check"], cwd=ROOT)
 
 
-@pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not installed")
+@abi_util.needs_hipcc
 def test_training_kernels_use_no_scratch():
     """The rule of tests/test_kernel_resources.py for the training library's translation unit (that test walks build.SOURCES only)."""
-    from orb_slam3_modified_amd.build import CSRC, FLAGS, TRAIN_SOURCE
-    flags = [f for f in FLAGS if f not in ("-shared", "-fPIC")]
-    tmp = tempfile.mkdtemp(prefix="orbx_train_asm_")
-    try:
-        out = os.path.join(tmp, "train.s")
-        subprocess.check_call(["hipcc"] + flags + ["-S", "--cuda-device-only", "-o", out, os.path.join(CSRC, TRAIN_SOURCE)])
-        asm = open(out).read()
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
-    kernels = re.findall(r"\.amdhsa_kernel\s+(\S+)", asm)
-    sizes = [int(x) for x in re.findall(r"\.amdhsa_private_segment_fixed_size\s+(\d+)", asm)]
-    assert len(kernels) >= 8 and len(sizes) == len(kernels)
-    assert not any(sizes), list(zip(kernels, sizes))
+    from orb_slam3_modified_amd.build import TRAIN_SOURCE
+    scratch = abi_util.kernel_scratch(TRAIN_SOURCE)   # one size per kernel, or it raises
+    assert len(scratch) >= 8
+    assert not any(scratch.values()), scratch
