@@ -16,6 +16,7 @@ DEBUG_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_debug.so")   #
 TRAIN_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_train.so")   # vocabulary training (include/orbx_train.h)
 STEREO_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_stereo.so")   # the batched stereo front-end (include/orbx_stereo.h)
 BOW_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_bow.so")         # the batched bag of words (include/orbx_bow.h)
+MATCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_match.so")     # the batched SearchByBoW (include/orbx_match.h)
 
 ORBX_OK, ORBX_E_INVALID, ORBX_E_EMPTY, ORBX_E_DEVICE, ORBX_E_CAPACITY, ORBX_E_FORMAT = 0, -1, -2, -3, -4, -5
 NUM_KERNELS = 6
@@ -260,8 +261,29 @@ def bow_lib() -> C.CDLL:
     return B
 
 
+class OrbxMatchSide(C.Structure):
+    """orbx_match_side (include/orbx_match.h)."""
+    _fields_ = [("d_kps", C.c_void_p), ("d_desc", C.c_void_p), ("d_counts", C.c_void_p), ("d_fv_node", C.c_void_p), ("d_fv_ptr", C.c_void_p),
+                ("d_fv_feat", C.c_void_p), ("d_fv_n", C.c_void_p), ("d_valid", C.c_void_p), ("nframes", C.c_int), ("capacity", C.c_int)]
+
+
+def match_lib() -> C.CDLL:
+    """liborbx_match.so.  `_orbx_match_symbols`: every name of include/orbx_match.h, bound here with its signature."""
+    vp, i32, f32, sp = C.c_void_p, C.c_int, C.c_float, C.POINTER(OrbxMatchSide)
+    sig = {
+        "orbx_match_create": (i32, [C.POINTER(vp), i32]),
+        "orbx_match_destroy": (None, [vp]),
+        "orbx_match_last_error": (C.c_char_p, [vp]),
+        "orbx_match_bow_pairs_device": (i32, [vp, sp, sp, vp, i32, i32, f32, i32, vp, vp, vp, vp]),
+        "orbx_match_bow_pairs": (i32, [vp, sp, sp, vp, i32, i32, f32, i32, vp, vp, vp]),
+    }
+    M = _load_side(MATCH_LIB_PATH, sig)
+    M._orbx_match_symbols = tuple(sig)
+    return M
+
+
 class SideHandle:
-    """A handle of a side library whose entry points are <prefix>_create / _destroy / _last_error (StereoBatch, BowBatch)."""
+    """A handle of a side library whose entry points are <prefix>_create / _destroy / _last_error (StereoBatch, BowBatch, MatchBatch)."""
 
     def __init__(self, library: C.CDLL, prefix: str, *create_args):
         self._L, self._prefix, self._h = library, prefix, C.c_void_p(0)

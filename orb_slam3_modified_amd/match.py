@@ -1,0 +1,114 @@
+"""The batched SearchByBoW over liborbx_match.so (include/orbx_match.h): ORBmatcher::SearchByBoW (src/ORBmatcher.cc:223-425, :765-905) for P
+(frame, frame) pairs at once on the descriptors, keypoints and FeatureVectors a batch extraction and BowBatch.transform_device left in HBM.
+All arithmetic runs in the HIP kernel of the library; this file only marshals buffers."""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+
+from . import _lib
+from ._lib import KP_DTYPE, OrbxMatchSide, ptr
+
+FRAME, KEYFRAMES = 0, 1   # ORBX_MATCH_FRAME, ORBX_MATCH_KEYFRAMES
+
+
+def _addr(t) -> int:
+    """An address: a torch tensor's data_ptr(), a numpy array's buffer, an int, or None (0)."""
+    if t is None:
+        return 0
+    if isinstance(t, np.ndarray):
+        return int(t.ctypes.data)
+    return int(t.data_ptr()) if hasattr(t, "data_ptr") else int(t)
+
+
+@dataclass
+class MatchSide:
+    """One side of the pairs (orbx_match_side): kps [F, cap] keypoints (28 bytes each), desc [F, cap, 32], counts [F, 2], the four
+    FeatureVector arrays as BowDeviceResult holds them, valid [F, cap] uint8 or None.  Torch tensors or raw HBM addresses for
+    bow_pairs_device, numpy arrays for bow_pairs."""
+    kps: object
+    desc: object
+    counts: object
+    fv_node: object
+    fv_ptr: object
+    fv_feat: object
+    fv_n: object
+    nframes: int
+    capacity: int
+    valid: object = None
+
+    @classmethod
+    def of(cls, kps, desc, counts, fv, nframes: int, capacity: int, valid=None) -> "MatchSide":
+        """From a batch extraction's buffers and a BowDeviceResult (or anything with fv_node / fv_ptr / fv_feat / fv_n)."""
+        return cls(kps, desc, counts, fv.fv_node, fv.fv_ptr, fv.fv_feat, fv.fv_n, int(nframes), int(capacity), valid)
+
+    def _struct(self) -> OrbxMatchSide:
+        return OrbxMatchSide(*(_addr(t) or None for t in (self.kps, self.desc, self.counts, self.fv_node, self.fv_ptr, self.fv_feat, self.fv_n,
+                                                           self.valid)), int(self.nframes), int(self.capacity))
+
+    def _host(self) -> "MatchSide":
+        """Contiguous numpy arrays of the ABI's element types."""
+        F, cap = int(self.nframes), int(self.capacity)
+        kps = np.ascontiguousarray(self.kps)
+        assert kps.nbytes == F * cap * KP_DTYPE.itemsize
+        a = lambda x, dt, *shape: np.ascontiguousarray(x, dt).reshape(shape)   # noqa: E731
+        return MatchSide(kps, a(self.desc, np.uint8, F, cap, 32), a(self.counts, np.int32, F, 2), a(self.fv_node, np.uint32, F, cap),
+                         a(self.fv_ptr, np.int32, F, cap + 1), a(self.fv_feat, np.uint32, F, cap), a(self.fv_n, np.int32, F), F, cap,
+                         None if self.valid is None else a(self.valid, np.uint8, F, cap))
+
+
+@dataclass
+class MatchResult:
+    """nmatches [P] (the reference's return value, -1 for a malformed pair), b2a [P, b.capacity], a2b [P, a.capacity] (-1: no match); torch
+    tensors from bow_pairs_device, numpy arrays from bow_pairs.  result[p] = (nmatches, b2a row, a2b row) of pair p on the host."""
+    nmatches: object
+    b2a: object
+    a2b: object
+
+    def __len__(self) -> int:
+        return int(self.nmatches.shape[0])
+
+    def __getitem__(self, p: int):
+        h = lambda t: None if t is None else (t if isinstance(t, np.ndarray) else t.cpu().numpy())   # noqa: E731
+        n, b, a = h(self.nmatches[p:p + 1]), h(None if self.b2a is None else self.b2a[p]), h(None if self.a2b is None else self.a2b[p])
+        return int(n[0]), b, a
+
+
+class MatchBatch(_lib.SideHandle):
+    """Putative matches for batches of frame pairs; one handle holds one stream and its scratch on one GPU."""
+
+    def __init__(self, device_id: int = 0):
+        self._M = _lib.match_lib()
+        self.device_id = int(device_id)
+        super().__init__(self._M, "orbx_match", int(device_id))
+
+    def bow_pairs_device(self, a: MatchSide, b: MatchSide, pairs, mode: int = FRAME, nn_ratio: float = 0.7, check_orientation: bool = True,
+                         stream=None, out: Optional[MatchResult] = None, npairs: Optional[int] = None) -> MatchResult:
+        """orbx_match_bow_pairs_device: `pairs` [P, 2] int32 (frame of a, frame of b) on the device; asynchronous on `stream` (None or 0: the
+        handle's own).  Without `out` the result tensors are allocated on the pairs' device (torch)."""
+        P = int(pairs.shape[0]) if npairs is None else int(npairs)
+        if out is None:
+            import torch
+            dev = pairs.device if hasattr(pairs, "device") else torch.device("cuda", self.device_id)
+            out = MatchResult(torch.empty(P, dtype=torch.int32, device=dev), torch.empty((P, b.capacity), dtype=torch.int32, device=dev),
+                              torch.empty((P, a.capacity), dtype=torch.int32, device=dev))
+        sa, sb = a._struct(), b._struct()
+        self._check(self._M.orbx_match_bow_pairs_device(self._h, C.byref(sa), C.byref(sb), ptr(_addr(pairs)), P, int(mode), float(nn_ratio),
+                                                        int(bool(check_orientation)), ptr(_addr(out.b2a)), ptr(_addr(out.a2b)),
+                                                        ptr(_addr(out.nmatches)), ptr(int(stream or 0))))
+        return out
+
+    def bow_pairs(self, a: MatchSide, b: MatchSide, pairs, mode: int = FRAME, nn_ratio: float = 0.7, check_orientation: bool = True) -> MatchResult:
+        """orbx_match_bow_pairs on numpy arrays of the same layout; returns when the results are on the host."""
+        ha = a._host()
+        hb = ha if b is a else b._host()
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        P = len(pairs)
+        out = MatchResult(np.zeros(P, np.int32), np.zeros((P, hb.capacity), np.int32), np.zeros((P, ha.capacity), np.int32))
+        sa, sb = ha._struct(), hb._struct()
+        self._check(self._M.orbx_match_bow_pairs(self._h, C.byref(sa), C.byref(sb), ptr(pairs), P, int(mode), float(nn_ratio),
+                                                 int(bool(check_orientation)), ptr(out.b2a), ptr(out.a2b), ptr(out.nmatches)))
+        return out
