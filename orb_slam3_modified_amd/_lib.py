@@ -17,6 +17,7 @@ TRAIN_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_train.so")   #
 STEREO_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_stereo.so")   # the batched stereo front-end (include/orbx_stereo.h)
 BOW_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_bow.so")         # the batched bag of words (include/orbx_bow.h)
 MATCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_match.so")     # the batched SearchByBoW (include/orbx_match.h)
+INITMATCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_initmatch.so")   # the batched SearchForInitialization (include/orbx_initmatch.h)
 
 ORBX_OK, ORBX_E_INVALID, ORBX_E_EMPTY, ORBX_E_DEVICE, ORBX_E_CAPACITY, ORBX_E_FORMAT = 0, -1, -2, -3, -4, -5
 NUM_KERNELS = 6
@@ -282,8 +283,30 @@ def match_lib() -> C.CDLL:
     return M
 
 
+class OrbxInitMatchSide(C.Structure):
+    """orbx_initmatch_side (include/orbx_initmatch.h)."""
+    _fields_ = [("d_kps", C.c_void_p), ("d_desc", C.c_void_p), ("d_counts", C.c_void_p), ("nframes", C.c_int), ("capacity", C.c_int)]
+
+
+def initmatch_lib(path: str = INITMATCH_LIB_PATH) -> C.CDLL:
+    """liborbx_initmatch.so.  `_orbx_initmatch_symbols`: every name of include/orbx_initmatch.h, bound here with its signature.  `path`: a
+    timing build of the same source (tools/initmatch_times.py)."""
+    vp, i32, f32, sp, fp = C.c_void_p, C.c_int, C.c_float, C.POINTER(OrbxInitMatchSide), C.POINTER(C.c_float)
+    sig = {
+        "orbx_initmatch_create": (i32, [C.POINTER(vp), i32]),
+        "orbx_initmatch_destroy": (None, [vp]),
+        "orbx_initmatch_last_error": (C.c_char_p, [vp]),
+        "orbx_initmatch_pairs_device": (i32, [vp, sp, sp, vp, i32, fp, i32, f32, i32, vp, vp, vp, vp, vp]),
+        "orbx_initmatch_pairs": (i32, [vp, sp, sp, vp, i32, fp, i32, f32, i32, vp, vp, vp, vp]),
+    }
+    M = _load_side(path, sig)
+    M._orbx_initmatch_symbols = tuple(sig)
+    return M
+
+
 class SideHandle:
-    """A handle of a side library whose entry points are <prefix>_create / _destroy / _last_error (StereoBatch, BowBatch, MatchBatch)."""
+    """A handle of a side library whose entry points are <prefix>_create / _destroy / _last_error (StereoBatch, BowBatch, MatchBatch,
+    InitMatchBatch)."""
 
     def __init__(self, library: C.CDLL, prefix: str, *create_args):
         self._L, self._prefix, self._h = library, prefix, C.c_void_p(0)

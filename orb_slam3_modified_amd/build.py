@@ -8,6 +8,7 @@ LIBS is the one place that knows them, one record per library; what is stale, wh
   liborbx_stereo.so  the batched stereo front-end (include/orbx_stereo.h)
   liborbx_bow.so     the batched bag of words (include/orbx_bow.h)
   liborbx_match.so   the batched SearchByBoW (include/orbx_match.h)
+  liborbx_initmatch.so  the batched SearchForInitialization (include/orbx_initmatch.h)
 The libraries beside the product link liborbx.so and use its ABI (and orbx_internal.h where they read a context's buffers).  Their sources sit
 in subdirectories of csrc/, outside kernels_hash(): the committed counter files measure the product's kernels, which they do not change.
 A new one is one more record ("Adding a side library")."""
@@ -32,6 +33,8 @@ BOW_OUT = os.path.join(os.path.dirname(OUT), "liborbx_bow.so")
 BOW_SOURCE = os.path.join("bow", "orbx_bow.hip")
 MATCH_OUT = os.path.join(os.path.dirname(OUT), "liborbx_match.so")
 MATCH_SOURCE = os.path.join("match", "orbx_match.hip")
+INITMATCH_OUT = os.path.join(os.path.dirname(OUT), "liborbx_initmatch.so")
+INITMATCH_SOURCE = os.path.join("initmatch", "orbx_initmatch.hip")
 
 
 class Lib(NamedTuple):
@@ -47,8 +50,9 @@ LIBS = (Lib(OUT, tuple(SOURCES)),
         Lib(TRAIN_OUT, (TRAIN_SOURCE,), product=True),
         Lib(STEREO_OUT, (STEREO_SOURCE,), hidden=True, product=True),
         Lib(BOW_OUT, (BOW_SOURCE,), hidden=True, product=True),
-        Lib(MATCH_OUT, (MATCH_SOURCE,), hidden=True, product=True))
-HEADERS = ("orbx.h", "orbx_debug.h", "orbx_train.h", "orbx_stereo.h", "orbx_bow.h", "orbx_match.h")
+        Lib(MATCH_OUT, (MATCH_SOURCE,), hidden=True, product=True),
+        Lib(INITMATCH_OUT, (INITMATCH_SOURCE,), hidden=True, product=True))
+HEADERS = ("orbx.h", "orbx_debug.h", "orbx_train.h", "orbx_stereo.h", "orbx_bow.h", "orbx_match.h", "orbx_initmatch.h")
 # -ffp-contract=off: the float paths (fastAtan2 polynomial, BRIEF rotation) must not be fused into FMAs,
 # the CPU reference evaluates them as separate IEEE operations (DESIGN.md "bit-exactness").
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall",

@@ -1,0 +1,347 @@
+"""The batched SearchForInitialization (liborbx_initmatch.so, orb_slam3_modified_amd/initmatch.py) on the GPU: for every pair
+(nmatches, matches12, prev row) equal the oracle's ORBmatcher::SearchForInitialization and the per-pair orbx_search_for_initialization, on the
+buffers a batch extraction left in HBM.  All comparisons are exact."""
+import ctypes as C
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+
+from oracle import pyoracle as po
+from orb_slam3_modified_amd import ORBextractor, ORBmatcher, OrbxError, _lib, synth
+from orb_slam3_modified_amd._lib import KP_DTYPE
+from orb_slam3_modified_amd.initmatch import LDS_MAX, InitMatchBatch, InitResult, InitSide, lds_bytes
+from tests import initmatch_model as im
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+
+EUROC = (480, 752, (1000, 1.2, 8, 20, 7))
+VGA5K = (480, 640, (5000, 1.2, 8, 20, 7))
+ONELEVEL = (480, 752, (1000, 1.2, 1, 20, 7))
+
+
+def _dev():
+    return torch.device("cuda", 0)
+
+
+def _bounds(shape, beyond):
+    H, W = shape[0], shape[1]
+    return (-20.5, -10.25, W + 31.5, H + 17.75) if beyond else (0.0, 0.0, float(W), float(H))
+
+
+class Batch:
+    """B frames extracted into HBM and their host copies."""
+
+    def __init__(self, ex, imgs, sync=True):
+        B, H, W = imgs.shape
+        self.ex, self.B, self.cap, self.shape = ex, B, ex.capacity, (H, W)
+        self.s = torch.cuda.Stream(device=_dev())
+        t = torch.from_numpy(np.ascontiguousarray(imgs)).to(_dev())
+        self.kps = torch.zeros((B, self.cap, 28), dtype=torch.uint8, device=_dev())
+        self.desc = torch.zeros((B, self.cap, 32), dtype=torch.uint8, device=_dev())
+        self.counts = torch.zeros((B, 2), dtype=torch.int32, device=_dev())
+        torch.cuda.synchronize()
+        ex.extract_batch_device(t.data_ptr(), B, H, W, W, H * W, self.kps.data_ptr(), self.desc.data_ptr(), self.counts.data_ptr(), (0, 1000),
+                                stream=self.s.cuda_stream)
+        self._imgs = t
+        if sync:
+            self.fetch()
+
+    def fetch(self):
+        self.s.synchronize()
+        self.hk = self.kps.cpu().numpy().view(KP_DTYPE).reshape(self.B, self.cap)
+        self.hd, self.hc = self.desc.cpu().numpy(), self.counts.cpu().numpy()
+
+    def side(self, lo=0, hi=None, counts=None):
+        hi = self.B if hi is None else hi
+        return InitSide(self.kps[lo:hi], self.desc[lo:hi], self.counts[lo:hi] if counts is None else counts, hi - lo, self.cap)
+
+    def frame(self, f):
+        n = int(self.hc[f, 0])
+        return self.hk[f, :n], self.hd[f, :n]
+
+    def prev(self, pairs, seed):
+        """A vbPrevMatched per pair: F1's positions moved by up to 12 pixels, the rows past the count filled with a pattern."""
+        rng = np.random.default_rng(seed)
+        p = np.full((len(pairs), self.cap, 2), -777.25, np.float32)
+        for i, (ia, _) in enumerate(np.asarray(pairs).tolist()):
+            n = int(self.hc[ia, 0])
+            p[i, :n, 0], p[i, :n, 1] = self.hk[ia, :n]["x"], self.hk[ia, :n]["y"]
+            p[i, :n] += rng.uniform(-12, 12, (n, 2)).astype(np.float32)
+        return p
+
+
+@pytest.fixture(scope="module")
+def euroc():
+    ex = ORBextractor(*EUROC[2], device_id=0)
+    bt = Batch(ex, synth.make_stream(256, EUROC[0], EUROC[1]))
+    assert (bt.hc[:, 0] > 800).all()
+    return bt
+
+
+def _pairs256():
+    """200 x (f, f + 1), 24 x (f, f + 5), 8 x (f, f), frame 7 against 24 others."""
+    p = [(f, f + 1) for f in range(200)] + [(f, f + 5) for f in range(0, 240, 10)] + [(f, f) for f in range(3, 256, 32)]
+    p += [(7, g) for g in range(8, 32)]
+    assert len(p) == 256
+    return np.array(p, np.int32)
+
+
+def _run(mb, a, b, pairs, bounds, window, ratio, ori, prev, stream, m21=True):
+    """-> nmatches, matches12, matches21 (or None), prev after the call (or None), on the host."""
+    P = len(pairs)
+    tp = torch.from_numpy(np.ascontiguousarray(pairs, np.int32)).to(_dev())
+    tprev = None if prev is None else torch.from_numpy(np.ascontiguousarray(prev, np.float32)).to(_dev())
+    out = InitResult(torch.full((P,), -9, dtype=torch.int32, device=_dev()), torch.full((P, a.capacity), -9, dtype=torch.int32, device=_dev()),
+                     torch.full((P, b.capacity), -9, dtype=torch.int32, device=_dev()) if m21 else None)
+    torch.cuda.synchronize()
+    mb.pairs_device(a, b, tp, bounds, window, ratio, ori, prev_xy=tprev, stream=stream.cuda_stream, out=out)
+    stream.synchronize()
+    return (out.nmatches.cpu().numpy(), out.matches12.cpu().numpy(), out.matches21.cpu().numpy() if m21 else None,
+            None if prev is None else tprev.cpu().numpy())
+
+
+def _check_pair(got, i, prev_in, bta, ia, btb, ib, bounds, window, ratio, ori, where, matcher=None):
+    """Pair i of a call's results against the oracle (and the per-pair entry point of the existing path): whole rows."""
+    n, m12, m21, prev_out = got
+    (k1, d1), (k2, d2) = bta.frame(ia), btb.frame(ib)
+    n1, n2 = len(k1), len(k2)
+    p0 = np.stack([k1["x"], k1["y"]], 1).astype(np.float32) if prev_in is None else prev_in[i, :n1]
+    on, om12, oprev = po.search_for_initialization(k1, d1, k2, d2, bounds, p0, window, ratio, ori)
+    assert n[i] == on, where
+    assert np.array_equal(m12[i, :n1], om12) and (m12[i, n1:] == -1).all(), where
+    if m21 is not None:
+        assert np.array_equal(m21[i, :n2], im.invert(om12, n2)) and (m21[i, n2:] == -1).all(), where
+    if prev_in is not None:
+        assert prev_out[i, :n1].tobytes() == oprev.tobytes(), where
+        assert prev_out[i, n1:].tobytes() == prev_in[i, n1:].tobytes(), where
+        keep = om12 < 0                                         # the rows of unmatched queries are unchanged, byte for byte
+        assert prev_out[i, :n1][keep].tobytes() == prev_in[i, :n1][keep].tobytes(), where
+    if matcher is not None:
+        pv = p0.copy()
+        sn, sm12 = matcher.SearchForInitialization(SimpleNamespace(mvKeysUn=k1, mDescriptors=d1, bounds=bounds),
+                                                   SimpleNamespace(mvKeysUn=k2, mDescriptors=d2, bounds=bounds), pv, window)
+        assert sn == on and np.array_equal(sm12, om12) and pv.tobytes() == oprev.tobytes(), where + ("orbx_search_for_initialization",)
+    return on
+
+
+# window, ratio, orientation, prev given, bounds beyond the image
+COMBOS = [(100, 0.9, True, False, False), (30, 0.6, False, True, True), (200, 0.9, True, True, False), (100, 0.1, True, False, True),
+          (200, 0.6, False, False, False), (30, 0.9, True, True, False), (100, 0.6, True, True, True), (200, 0.1, False, True, False)]
+
+
+def test_parity_per_pair_on_256_frames(euroc):
+    bt = euroc
+    mb = InitMatchBatch(0)
+    assert lds_bytes(bt.cap, bt.cap) <= LDS_MAX                   # this capacity runs in LDS
+    p256 = _pairs256()
+    small = np.array([(0, 1), (10, 15), (20, 20), (7, 9), (7, 30), (100, 101), (250, 255)], np.int32)
+    for step, (window, ratio, ori, given, beyond) in enumerate(COMBOS):
+        bounds = _bounds(bt.shape, beyond)
+        m = ORBmatcher(bt.ex, ratio, ori)
+        for pairs, split in ((p256, False), (small, False), (None, True)):
+            if split:        # A and B as two batches: B is the upper half of the frames
+                a, b, off = bt.side(0, 128), bt.side(128, 256), 128
+                pairs = np.array([(0, 1), (10, 15), (20, 20), (7, 9), (7, 30), (100, 101), (120, 127)], np.int32)
+            else:
+                a, b, off = bt.side(), bt.side(), 0
+            if len(pairs) == 256 and step >= 4:
+                continue                                          # the large set under the first four combinations
+            prev = bt.prev(pairs, 100 + step) if given else None
+            got = _run(mb, a, b, pairs, bounds, window, ratio, ori, prev, bt.s)
+            total = 0
+            for i, (ia, ib) in enumerate(pairs.tolist()):
+                per_pair = m if (len(pairs) != 256 or i % 23 == 0) else None
+                total += _check_pair(got, i, prev, bt, ia, bt, ib + off, bounds, window, ratio, ori, (step, len(pairs), split, i), per_pair)
+            if len(pairs) == 256 and (window, ratio) == (100, 0.9):
+                assert total > 256 * 20, total                    # the oracle finds matches on these frames
+    mb.close()
+
+
+def test_prev_chained_through_three_calls(euroc):
+    """F1 against three successive frames with vbPrevMatched carried over on the device (src/Tracking.cc:2470-2495)."""
+    bt = euroc
+    mb = InitMatchBatch(0)
+    bounds = _bounds(bt.shape, False)
+    firsts = list(range(0, 240, 30))
+    prev_h = np.zeros((len(firsts), bt.cap, 2), np.float32)
+    for i, f in enumerate(firsts):
+        prev_h[i, :, 0], prev_h[i, :, 1] = bt.hk[f]["x"], bt.hk[f]["y"]
+    tprev = torch.from_numpy(prev_h).to(_dev())
+    oprev = [prev_h[i, :int(bt.hc[f, 0])].copy() for i, f in enumerate(firsts)]
+    outs = []
+    tps = [torch.tensor([(f, f + step) for f in firsts], dtype=torch.int32).to(_dev()) for step in (1, 2, 3)]
+    torch.cuda.synchronize()
+    for tp in tps:                                                # three calls queued without a host sync between them
+        outs.append(mb.pairs_device(bt.side(), bt.side(), tp, bounds, 100, 0.9, True, prev_xy=tprev, stream=bt.s.cuda_stream))
+    bt.s.synchronize()
+    for step, out in zip((1, 2, 3), outs):
+        n, m12 = out.nmatches.cpu().numpy(), out.matches12.cpu().numpy()
+        for i, f in enumerate(firsts):
+            (k1, d1), (k2, d2) = bt.frame(f), bt.frame(f + step)
+            on, om12, oprev[i] = po.search_for_initialization(k1, d1, k2, d2, bounds, oprev[i], 100, 0.9, True)
+            assert n[i] == on and np.array_equal(m12[i, :len(k1)], om12), (step, f)
+    final = tprev.cpu().numpy()
+    for i, f in enumerate(firsts):
+        assert final[i, :len(oprev[i])].tobytes() == oprev[i].tobytes(), f
+    mb.close()
+
+
+@pytest.mark.parametrize("cfg,nframes", [(VGA5K, 4), (ONELEVEL, 8)])
+def test_other_extractors(cfg, nframes):
+    """The initialisation extractor (5000 features: the global-memory path, not forced) and a one-level extractor (every feature level 0)."""
+    ex = ORBextractor(*cfg[2], device_id=0)
+    bt = Batch(ex, synth.make_stream(nframes, cfg[0], cfg[1]))
+    if cfg is VGA5K:
+        assert (bt.hc[:, 0] > 3000).all() and lds_bytes(bt.cap, bt.cap) > LDS_MAX
+    else:
+        assert all((bt.hk[f, :bt.hc[f, 0]]["octave"] == 0).all() for f in range(bt.B)) and (bt.hc[:, 0] > 500).all()
+    mb = InitMatchBatch(0)
+    pairs = np.array([(0, 1), (1, 2), (2, 2), (0, 3)], np.int32)
+    for step, (window, ratio, ori, given, beyond) in enumerate(COMBOS[:5]):
+        bounds = _bounds(bt.shape, beyond)
+        prev = bt.prev(pairs, 40 + step) if given else None
+        got = _run(mb, bt.side(), bt.side(), pairs, bounds, window, ratio, ori, prev, bt.s)
+        m = ORBmatcher(ex, ratio, ori)
+        total = sum(_check_pair(got, i, prev, bt, ia, bt, ib, bounds, window, ratio, ori, (cfg[2], step, i), m if i == 0 else None)
+                    for i, (ia, ib) in enumerate(pairs.tolist()))
+        assert total > 0
+    mb.close()
+
+
+def test_both_paths_give_the_same_bytes(euroc, monkeypatch):
+    bt = euroc
+    pairs = _pairs256()[::8]
+    default = InitMatchBatch(0)
+    handles = {}
+    # "chunks": the smallest LDS block the LDS path takes: the candidate room is one query's longest list, so every pair runs in many chunks
+    for name, limit in (("global", 0), ("chunks", lds_bytes(bt.cap, bt.cap))):
+        monkeypatch.setenv("ORBX_INITMATCH_LDS", str(limit))
+        handles[name] = InitMatchBatch(0)
+        monkeypatch.delenv("ORBX_INITMATCH_LDS")
+    for window, ratio, ori, given, beyond in COMBOS[:4]:
+        bounds = _bounds(bt.shape, beyond)
+        prev = bt.prev(pairs, 7) if given else None
+        ref = _run(default, bt.side(), bt.side(), pairs, bounds, window, ratio, ori, prev, bt.s)
+        assert (ref[0] > 0).any()
+        for name, h in handles.items():
+            got = _run(h, bt.side(), bt.side(), pairs, bounds, window, ratio, ori, prev, bt.s)
+            for x, y in zip(ref, got):
+                assert (x is None and y is None) or x.tobytes() == y.tobytes(), (name, window, ratio, ori)
+    for h in list(handles.values()) + [default]:
+        h.close()
+
+
+def test_malformed_pairs(euroc):
+    bt = euroc
+    mb = InitMatchBatch(0)
+    F = 12
+    counts = bt.counts[:F].clone()
+    counts[3, 0] = -1                                     # a negative count (an overflowed frame)
+    counts[5, 0] = bt.cap + 1                             # a count above the capacity
+    bad_side, good = bt.side(0, F, counts), bt.side(0, F)
+    pairs = np.array([(0, 1), (0, F), (1, 2), (-1, 1), (2, 3), (3, 4), (4, 6), (5, 6), (6, 5), (6, 7), (F + 100, 0), (10, 11)], np.int32)
+    bad = {1, 3, 4, 5, 7, 8, 10}
+    bounds = _bounds(bt.shape, False)
+    prev = bt.prev(np.clip(pairs, 0, F - 1), 3)
+    n, m12, m21, pv = _run(mb, bad_side, bad_side, pairs, bounds, 100, 0.9, True, prev, bt.s)
+    wn, wm12, wm21, wpv = _run(mb, good, good, np.clip(pairs, 0, F - 1), bounds, 100, 0.9, True, prev, bt.s)
+    for i in range(len(pairs)):
+        if i in bad:
+            assert n[i] == -1 and (m12[i] == -1).all() and (m21[i] == -1).all() and pv[i].tobytes() == prev[i].tobytes(), i
+        else:                                             # the neighbours are what they are without the malformed pairs
+            assert n[i] == wn[i] > 0 and np.array_equal(m12[i], wm12[i]) and np.array_equal(m21[i], wm21[i]) and pv[i].tobytes() == wpv[i].tobytes(), i
+    # matches21 NULL is accepted
+    n2, m12b, none, pv2 = _run(mb, bad_side, bad_side, pairs, bounds, 100, 0.9, True, prev, bt.s, m21=False)
+    assert none is None and np.array_equal(n2, n) and np.array_equal(m12b, m12) and pv2.tobytes() == pv.tobytes()
+    # what the host can check: ORBX_E_INVALID with a reason
+    M = _lib.initmatch_lib()
+    sa = good._struct()
+    tp = torch.from_numpy(pairs).to(_dev())
+    o12 = torch.zeros((len(pairs), bt.cap), dtype=torch.int32, device=_dev())
+    onm = torch.zeros(len(pairs), dtype=torch.int32, device=_dev())
+    p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
+    fb = lambda *v: (C.c_float * 4)(*v)      # noqa: E731
+    ok = [C.byref(sa), C.byref(sa), p(tp), len(pairs), fb(*bounds), 100, 0.9, 1, None, p(o12), None, p(onm), None]
+    assert M.orbx_initmatch_pairs_device(mb._h, *ok) == 0
+    for idx, v in ((0, None), (1, None), (2, None), (3, 0), (3, -2), (4, None), (4, fb(752, 0, 0, 480)), (4, fb(0, 480, 752, 480)), (5, -1), (9, None),
+                   (11, None)):
+        a_ = list(ok)
+        a_[idx] = v
+        assert M.orbx_initmatch_pairs_device(mb._h, *a_) == _lib.ORBX_E_INVALID, (idx, v)
+        assert len(M.orbx_initmatch_last_error(mb._h)) > 10
+    for field, v in (("d_desc", None), ("d_counts", None), ("nframes", 0), ("capacity", 0), ("capacity", 32769), ("d_kps", None)):
+        sb = good._struct()
+        setattr(sb, field, v)
+        a_ = list(ok)
+        a_[1] = C.byref(sb)
+        assert M.orbx_initmatch_pairs_device(mb._h, *a_) == _lib.ORBX_E_INVALID, field
+    with pytest.raises(OrbxError):
+        mb.pairs_device(good, good, tp, bounds, -5, 0.9, True)
+    bt.s.synchronize()
+    mb.close()
+    mb.close()
+
+
+def test_host_form_equals_device_form(euroc):
+    bt = euroc
+    mb = InitMatchBatch(0)
+    F = 9
+    pairs = np.array([(0, 1), (1, 0), (4, 4), (2, 8), (8, 3)], np.int32)
+    bounds = _bounds(bt.shape, True)
+    hs = InitSide(bt.hk[:F], bt.hd[:F], bt.hc[:F], F, bt.cap)
+    for window, ratio, ori, given in ((100, 0.9, True, True), (30, 0.6, False, False)):
+        prev = bt.prev(pairs, 9) if given else None
+        r = mb.pairs(hs, hs, pairs, bounds, window, ratio, ori, prev_xy=prev)
+        n, m12, m21, pv = _run(mb, bt.side(0, F), bt.side(0, F), pairs, bounds, window, ratio, ori, prev, bt.s)
+        assert np.array_equal(r.nmatches, n) and np.array_equal(r.matches12, m12) and np.array_equal(r.matches21, m21) and (n > 0).all()
+        if given:
+            assert r.prev_xy.tobytes() == pv.tobytes() and r.prev_xy.tobytes() != prev.tobytes()
+        else:
+            assert r.prev_xy is None
+        k, r12, r21 = r[2]
+        assert k == n[2] and np.array_equal(r12, m12[2]) and np.array_equal(r21, m21[2])
+    mb.close()
+
+
+def test_two_handles_on_two_streams(euroc):
+    """Two handles run at the same time on two streams and give what each gives alone."""
+    bt = euroc
+    bounds = _bounds(bt.shape, False)
+    p1, p2 = _pairs256(), _pairs256()[::-1].copy()
+    alone = InitMatchBatch(0)
+    w1 = _run(alone, bt.side(), bt.side(), p1, bounds, 100, 0.9, True, None, bt.s)
+    w2 = _run(alone, bt.side(), bt.side(), p2, bounds, 200, 0.6, False, None, bt.s)
+    alone.close()
+    h1, h2 = InitMatchBatch(0), InitMatchBatch(0)
+    s1, s2 = torch.cuda.Stream(device=_dev()), torch.cuda.Stream(device=_dev())
+    t1, t2 = torch.from_numpy(p1).to(_dev()), torch.from_numpy(p2).to(_dev())
+    torch.cuda.synchronize()
+    r1 = h1.pairs_device(bt.side(), bt.side(), t1, bounds, 100, 0.9, True, stream=s1.cuda_stream)
+    r2 = h2.pairs_device(bt.side(), bt.side(), t2, bounds, 200, 0.6, False, stream=s2.cuda_stream)
+    s1.synchronize()
+    s2.synchronize()
+    for r, w in ((r1, w1), (r2, w2)):
+        assert np.array_equal(r.nmatches.cpu().numpy(), w[0]) and np.array_equal(r.matches12.cpu().numpy(), w[1])
+        assert np.array_equal(r.matches21.cpu().numpy(), w[2])
+    h1.close()
+    h2.close()
+
+
+def test_a_call_is_ordered_after_the_extraction_on_its_stream():
+    """Extraction and matching queued on one stream of the caller, no host sync between them."""
+    ex = ORBextractor(*EUROC[2], device_id=0)
+    imgs = synth.make_stream(6, EUROC[0], EUROC[1])
+    bt = Batch(ex, imgs, sync=False)                              # the extraction is queued on bt.s, nothing has waited for it
+    mb = InitMatchBatch(0)
+    pairs = np.array([(0, 1), (1, 2), (2, 3), (3, 4), (4, 5)], np.int32)
+    bounds = _bounds(bt.shape, False)
+    with torch.cuda.stream(bt.s):
+        tp = torch.from_numpy(pairs).to(_dev(), non_blocking=True)
+    out = mb.pairs_device(bt.side(), bt.side(), tp, bounds, 100, 0.9, True, stream=bt.s.cuda_stream)
+    bt.fetch()
+    got = (out.nmatches.cpu().numpy(), out.matches12.cpu().numpy(), out.matches21.cpu().numpy(), None)
+    for i, (ia, ib) in enumerate(pairs.tolist()):
+        assert _check_pair(got, i, None, bt, ia, bt, ib, bounds, 100, 0.9, True, ("ordered", i)) > 0
+    mb.close()
