@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
-"""Randomised parity sweep of the extractor against the oracle (same generator as
-tests/test_gpu_extractor.py::test_random_shapes_and_parameters, more seeds): python tools/fuzz_extractor.py [first] [count] [--variants]
+"""Randomised parity sweep of the extractor against the oracle: python tools/fuzz_extractor.py [first] [count] [--variants]
+The generator of tests/test_gpu_extractor.py::test_random_shapes_and_parameters widened to the ABI's 1 .. 16 pyramid levels, with the side rule of
+tests/test_gpu_many_levels.py::test_random_shapes_at_nine_to_sixteen_levels: a scale factor whose top level of >= 67 px would need an image side above
+1400 px is redrawn from the front of the list (1.1 always fits), so no configuration leaves the documented limits.  More image kinds, more seeds.
 --variants: every configuration also draws a random OpenCV / build variant (gauss_kernel, gauss_round, gauss_tail, atan_fma, brief_fma —
 INTEGRATION.md section 6), set on the oracle and on the GPU context alike."""
 import os, sys
@@ -17,9 +19,16 @@ count = int(argv[1]) if len(argv) > 1 else 60
 bad = rejected = 0
 for seed in range(first, first + count):
     rng = np.random.default_rng(1000 + seed)
-    sf = float(np.float32(rng.choice([1.1, 1.15, 1.2, 1.25, 1.33, 1.5, 1.7, 1.9])))
-    nlev = int(rng.integers(1, 9))
-    lo = max(int(np.ceil(70 * sf ** (nlev - 1))) + 2, 90)
+    scales = [1.1, 1.15, 1.2, 1.25, 1.33, 1.5, 1.7, 1.9]
+    nlev = int(rng.integers(1, 17))
+    side = lambda s: int(np.ceil(70 * float(np.float32(s)) ** (nlev - 1))) + 2           # top level must keep >= 67 px   # noqa: E731
+    k = len(scales)
+    sf = scales[int(rng.integers(0, k))]
+    while side(sf) > 1400:
+        k -= 1
+        sf = scales[int(rng.integers(0, k))]
+    sf = float(np.float32(sf))
+    lo = max(side(sf), 90)
     rows = int(rng.integers(lo, max(700, lo + 200))); cols = int(rng.integers(lo, max(900, lo + 300)))
     if cols > 8 * rows or rows > 2 * cols:
         rows = cols = max(rows, cols) // 2 + lo
