@@ -353,6 +353,25 @@ def ptr(a) -> C.c_void_p:
     return C.c_void_p(int(a))
 
 
+def addr(t) -> int:
+    """An address: a torch tensor's data_ptr(), a numpy array's buffer, an int, or None (0)."""
+    if t is None:
+        return 0
+    if isinstance(t, np.ndarray):
+        return int(t.ctypes.data)
+    return int(t.data_ptr()) if hasattr(t, "data_ptr") else int(t)
+
+
+def host_array(x, dtype, *shape) -> np.ndarray:
+    """A contiguous numpy array of the ABI's element type and shape."""
+    return np.ascontiguousarray(x, dtype).reshape(shape)
+
+
+def host_view(t):
+    """A result (or a row of one) on the host: a numpy array as it is, a torch tensor copied, None as None."""
+    return None if t is None else (t if isinstance(t, np.ndarray) else t.cpu().numpy())
+
+
 def check(rc: int, ctx=None) -> int:
     if rc < 0:
         msg = ""

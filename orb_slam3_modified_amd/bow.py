@@ -9,17 +9,10 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import ptr
+from ._lib import addr, ptr
 
 BowVector = Tuple[np.ndarray, np.ndarray]
 FeatureVector = Dict[int, List[int]]
-
-
-def _addr(t) -> int:
-    """A device address: a torch tensor's data_ptr(), an int, or None (0)."""
-    if t is None:
-        return 0
-    return int(t.data_ptr()) if hasattr(t, "data_ptr") else int(t)
 
 
 @dataclass
@@ -97,8 +90,8 @@ class BowBatch(_lib.SideHandle):
                                   z(nframes, capacity, dt=torch.int32), z(nframes, dt=torch.int32))
         b = (out.bow_ids, out.bow_vals, out.bow_n) if bow else (None, None, None)
         v = (out.fv_node, out.fv_ptr, out.fv_feat, out.fv_n) if fv else (None, None, None, None)
-        self._check(self._B.orbx_bow_transform_batch_device(self._h, ptr(_addr(d_desc)), ptr(_addr(d_counts)), int(nframes), int(capacity),
-                                                            *(ptr(_addr(t)) for t in b + v), ptr(int(stream))))
+        self._check(self._B.orbx_bow_transform_batch_device(self._h, ptr(addr(d_desc)), ptr(addr(d_counts)), int(nframes), int(capacity),
+                                                            *(ptr(addr(t)) for t in b + v), ptr(int(stream))))
         return out
 
     # ---- scores ------------------------------------------------------------------------------------------
@@ -127,7 +120,7 @@ class BowBatch(_lib.SideHandle):
             import torch
             dev = q_ids.device if hasattr(q_ids, "device") else torch.device("cuda", 0)
             scores = torch.empty((nq, ndb), dtype=torch.float64, device=dev)
-        self._check(self._B.orbx_bow_score_matrix_device(self._h, ptr(_addr(q_ids)), ptr(_addr(q_vals)), ptr(_addr(q_n)), int(nq), int(q_stride),
-                                                         ptr(_addr(db_ids)), ptr(_addr(db_vals)), ptr(_addr(db_n)), int(ndb), int(db_stride),
-                                                         ptr(_addr(scores)), ptr(int(stream))))
+        self._check(self._B.orbx_bow_score_matrix_device(self._h, ptr(addr(q_ids)), ptr(addr(q_vals)), ptr(addr(q_n)), int(nq), int(q_stride),
+                                                         ptr(addr(db_ids)), ptr(addr(db_vals)), ptr(addr(db_n)), int(ndb), int(db_stride),
+                                                         ptr(addr(scores)), ptr(int(stream))))
         return scores

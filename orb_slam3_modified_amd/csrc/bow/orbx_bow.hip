@@ -252,8 +252,7 @@ struct orbx_bow : orbx::side::Handle {    // scratch: records [slots] + keys [2]
   orbx_voc* voc = nullptr;
   int levelsup = 0;
   int accumulate = 0, norm = kNormNone;   // learnt from orbx_bow_finalize at create
-  int lds_limit = kBowLds;                // ORBX_BOW_LDS at create
-  std::vector<uint8_t> h_io;              // the host forms' fixed-stride results before compaction
+  int lds_limit = kBowLds;                // ORBX_BOW_LDS at create; h_io: the host forms' fixed-stride results before compaction
 };
 
 namespace {
@@ -297,7 +296,7 @@ int orbx_bow_create(orbx_bow** out, orbx_voc* voc, int levelsup) {
   if (norm == kNormL2 && vals[0] != (added ? 2.0 / std::sqrt(8.0) : 1.0 / std::sqrt(5.0))) return bad("orbx_bow_finalize gave an unknown normalisation on the probe");
   orbx_bow* b = new orbx_bow();
   b->voc = voc; b->levelsup = levelsup; b->accumulate = added ? 1 : 0; b->norm = norm;
-  if (const char* e = std::getenv("ORBX_BOW_LDS")) b->lds_limit = std::max(0, std::min(kBowLds, std::atoi(e)));
+  b->lds_limit = env_int("ORBX_BOW_LDS", 0, kBowLds, kBowLds);
   if (const char* e = open_handle(b, device)) { orbx_bow_destroy(b); return bad(e, ORBX_E_DEVICE); }
   *out = b;
   return ORBX_OK;
@@ -324,14 +323,11 @@ int orbx_bow_transform_batch_device(orbx_bow* b, const uint8_t* d_desc, const in
   const int nf = (d_fv_node != nullptr) + (d_fv_ptr != nullptr) + (d_fv_feat != nullptr) + (d_fv_n != nullptr);
   if ((nb != 0 && nb != 3) || (nf != 0 && nf != 4)) return fail(b, ORBX_E_INVALID, std::string(who) + "an output group is partly null");
   if (nb == 0 && nf == 0) return fail(b, ORBX_E_INVALID, std::string(who) + "null outputs");
-  for (const void* p : {(const void*)d_desc, (const void*)d_counts, (const void*)d_bow_ids, (const void*)d_fv_node}) {
-    const int pd = pointer_device(p);
-    if (pd >= 0 && pd != b->device)
-      return fail(b, ORBX_E_INVALID, std::string(who) + "a buffer lives on device " + std::to_string(pd) + ", the vocabulary on device " + std::to_string(b->device));
-  }
+  int rc = same_device(b, who, {d_desc, d_counts, d_bow_ids, d_fv_node}, "the vocabulary");
+  if (rc != ORBX_OK) return rc;
   ORBX_SIDE_HIP(b, hipSetDevice(b->device));
   const size_t slots = (size_t)nframes * capacity;
-  int rc = grow(b, &b->scratch, scratch_layout(slots, nullptr, nullptr));
+  rc = grow(b, &b->scratch, scratch_layout(slots, nullptr, nullptr));
   if (rc != ORBX_OK) return rc;
   Scratch sc;
   scratch_layout(slots, &sc, b->scratch.p);
@@ -411,15 +407,11 @@ int orbx_bow_score_matrix_device(orbx_bow* b, const uint32_t* d_q_ids, const dou
   if (nq < 1 || ndb < 1 || q_stride < 1 || db_stride < 1) return fail(b, ORBX_E_INVALID, std::string(who) + "nq, ndb and the strides must be at least 1");
   if (nq > 65535) return fail(b, ORBX_E_INVALID, std::string(who) + "at most 65535 queries per call");
   if (!d_q_ids || !d_q_vals || !d_q_n || !d_db_ids || !d_db_vals || !d_db_n || !d_scores) return fail(b, ORBX_E_INVALID, std::string(who) + "null buffer");
-  for (const void* p : {(const void*)d_q_ids, (const void*)d_db_ids, (const void*)d_scores}) {
-    const int pd = pointer_device(p);
-    if (pd >= 0 && pd != b->device)
-      return fail(b, ORBX_E_INVALID, std::string(who) + "a buffer lives on device " + std::to_string(pd) + ", the vocabulary on device " + std::to_string(b->device));
-  }
+  int rc = same_device(b, who, {d_q_ids, d_db_ids, d_scores}, "the vocabulary");
+  if (rc != ORBX_OK) return rc;
   ORBX_SIDE_HIP(b, hipSetDevice(b->device));
   hipStream_t st = stream ? (hipStream_t)stream : b->st;
-  const int rc = wait_previous(b, st);
-  if (rc != ORBX_OK) return rc;
+  if ((rc = wait_previous(b, st)) != ORBX_OK) return rc;
   const BowbSide q = {d_q_ids, d_q_vals, d_q_n, nullptr, q_stride}, db = {d_db_ids, d_db_vals, d_db_n, nullptr, db_stride};
   hipLaunchKernelGGL(k_bowb_score, dim3((unsigned)((ndb + 255) / 256), (unsigned)nq), dim3(256), 0, st, q, db, ndb, d_scores);
   return record_call(b, st);

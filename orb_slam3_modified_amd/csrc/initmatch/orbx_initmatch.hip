@@ -21,15 +21,16 @@
 
 #include <algorithm>
 #include <climits>
-#include <cstdlib>
 #include <cstring>
 #include <string>
-#include <vector>
 
 #include "../side/orbx_handle.h"
+#include "../side/orbx_pair_device.h"
 #include "../../../include/orbx_initmatch.h"
 
 namespace {
+
+using namespace orbx::side::dev;          // ld / st on the chain's state: written by one lane, read by the wave's other lanes in the next step
 
 constexpr int kThreads = 512;             // 8 waves
 constexpr int kLdsMax = 152 * 1024;       // dynamic LDS of one workgroup (160 KiB per CU, the static part is below 4 KiB)
@@ -72,58 +73,8 @@ __host__ __device__ inline Lay layout(int capA, int capB, int p2, bool lds) {
   return l;
 }
 
-struct D8 { uint32_t w[8]; };
-__device__ __forceinline__ D8 load_desc(const uint8_t* p) {
-  const uint4 x = ((const uint4*)p)[0], y = ((const uint4*)p)[1];
-  D8 d;
-  d.w[0] = x.x; d.w[1] = x.y; d.w[2] = x.z; d.w[3] = x.w; d.w[4] = y.x; d.w[5] = y.y; d.w[6] = y.z; d.w[7] = y.w;
-  return d;
-}
-__device__ __forceinline__ int hamming(const D8& a, const D8& b) {
-  int s = 0;
-#pragma unroll
-  for (int k = 0; k < 8; k++) s += __popc(a.w[k] ^ b.w[k]);
-  return s;
-}
-
-// the minimum over the 64 lanes (all active), wave-uniform: four DPP steps leave each row of 16 lanes with its minimum, the four rows meet
-// through readlane
-__device__ __forceinline__ int wave_min(int v) {
-  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xF, 0xF, false));    // quad_perm [1, 0, 3, 2]
-  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x4E, 0xF, 0xF, false));    // quad_perm [2, 3, 0, 1]
-  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x141, 0xF, 0xF, false));   // row_half_mirror
-  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x140, 0xF, 0xF, false));   // row_mirror
-  return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
-             min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
-}
-
-// the chain's state is written by one lane and read by the wave's other lanes in the next step
-__device__ __forceinline__ int ld_state(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-__device__ __forceinline__ void st_state(int32_t* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-
-// the rotation histogram's bin (src/ORBmatcher.cc:718-725), -1 when it falls outside the 30 bins (then the match is never removed)
-__device__ __forceinline__ int rot_bin(float angle_a, float angle_b) {
-  float rot = angle_a - angle_b;
-  if (rot < 0.0f) rot += 360.0f;
-  const float r = roundf(rot * (1.0f / 30));
-  if (!(r >= 0.0f && r <= 30.0f)) return -1;
-  const int bin = (int)r;
-  return bin == 30 ? 0 : bin;
-}
-__device__ __forceinline__ float kp_f(const uint8_t* kps, size_t i, size_t field) { return *(const float*)(kps + i * sizeof(orbx_keypoint) + field); }
-__device__ __forceinline__ int kp_octave(const uint8_t* kps, size_t i) { return *(const int32_t*)(kps + i * sizeof(orbx_keypoint) + offsetof(orbx_keypoint, octave)); }
-constexpr size_t kX = offsetof(orbx_keypoint, x), kY = offsetof(orbx_keypoint, y), kAngle = offsetof(orbx_keypoint, angle);
-
-// n16 16-byte pieces from src to the LDS block at dst: piece i lands at dst + 16 i (lane-linear inside a wave, as the LDS-DMA load writes)
-__device__ __forceinline__ void stage_dma(uint8_t* dst, const uint8_t* src, int n16) {
-  for (int i0 = 0; i0 < n16; i0 += kThreads) {
-    const int i = i0 + (int)threadIdx.x;
-    uint8_t* d = dst + (size_t)(i0 + ((int)threadIdx.x & ~63)) * 16;   // wave-uniform; the hardware adds lane * 16
-    if (i < n16)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (size_t)i * 16),
-                                       (__attribute__((address_space(3))) void*)d, 16, 0, 0);
-  }
-}
+constexpr size_t kX = offsetof(orbx_keypoint, x), kY = offsetof(orbx_keypoint, y), kAngle = offsetof(orbx_keypoint, angle),
+                 kOctave = offsetof(orbx_keypoint, octave);
 
 // Frame::GetFeaturesInArea(x, y, r, 0, 0) over the sorted keys: emit(index) for every candidate, in the reference's order
 template <class F>
@@ -196,15 +147,15 @@ __global__ __launch_bounds__(kThreads) void k_init_pairs(Args g) {
     if (tid == 0) { s_cnt = 0; s_nm = 0; }
     if (tid < 32) s_hist[tid] = 0;
     if (LDS) {
-      stage_dma(base + L.dA, g.a.desc + oA * 32, nA * 2);
-      stage_dma(base + L.dB, g.b.desc + oB * 32, nB * 2);
+      stage_dma<kThreads>(base + L.dA, g.a.desc + oA * 32, nA * 2);
+      stage_dma<kThreads>(base + L.dB, g.b.desc + oB * 32, nB * 2);
     }
     for (int i = tid; i < nB; i += kThreads) { mdist[i] = INT_MAX; holder[i] = -1; }
     for (int i = tid; i < nA; i += kThreads) { m12[i] = -1; acc[i] = -1; }
     __syncthreads();                       // s_cnt = 0 before anyone adds to it
     for (int i = tid; i < nB; i += kThreads) {
-      if (kp_octave(kB, i) != 0) continue;
-      const float fx = roundf((kp_f(kB, i, kX) - g.minX) * g.invW), fy = roundf((kp_f(kB, i, kY) - g.minY) * g.invH);
+      if (kp_field<int32_t>(kB, i, kOctave) != 0) continue;
+      const float fx = roundf((kp_field<float>(kB, i, kX) - g.minX) * g.invW), fy = roundf((kp_field<float>(kB, i, kY) - g.minY) * g.invH);
       if (!(fx >= 0.0f && fx < (float)kCols && fy >= 0.0f && fy < (float)kRows)) continue;   // outside the grid (or NaN): in no cell
       const int k = atomicAdd(&s_cnt, 1);  // k < nB <= capB <= p2
       keys[k] = (uint32_t)((int)fx * kRows + (int)fy) << 16 | (uint32_t)i;
@@ -226,7 +177,7 @@ __global__ __launch_bounds__(kThreads) void k_init_pairs(Args g) {
       }
     for (int j = tid; j < n0; j += kThreads) {
       const size_t i = keys[j] & 0xFFFFu;
-      sxy[j] = make_float2(kp_f(kB, i, kX), kp_f(kB, i, kY));
+      sxy[j] = make_float2(kp_field<float>(kB, i, kX), kp_field<float>(kB, i, kY));
     }
     for (int c = tid; c <= kCells; c += kThreads) {
       const uint32_t want = (uint32_t)c << 16;
@@ -242,8 +193,8 @@ __global__ __launch_bounds__(kThreads) void k_init_pairs(Args g) {
     // ---- phase A: every query's candidate count, then the offsets
     for (int q = tid; q <= nA; q += kThreads) {
       int c = 0;
-      if (q < nA && kp_octave(kA, q) == 0) {
-        const float cx = prev ? prev[2 * q] : kp_f(kA, q, kX), cy = prev ? prev[2 * q + 1] : kp_f(kA, q, kY);
+      if (q < nA && kp_field<int32_t>(kA, q, kOctave) == 0) {
+        const float cx = prev ? prev[2 * q] : kp_field<float>(kA, q, kX), cy = prev ? prev[2 * q + 1] : kp_field<float>(kA, q, kY);
         walk(g, cx, cy, cstart, keys, sxy, [&](int) { c++; });
       }
       offs[q] = c;
@@ -285,7 +236,7 @@ __global__ __launch_bounds__(kThreads) void k_init_pairs(Args g) {
         int k = offs[q] - e0;
         const int kend = offs[q + 1] - e0;
         if (kend > k) {
-          const float cx = prev ? prev[2 * q] : kp_f(kA, q, kX), cy = prev ? prev[2 * q + 1] : kp_f(kA, q, kY);
+          const float cx = prev ? prev[2 * q] : kp_field<float>(kA, q, kX), cy = prev ? prev[2 * q + 1] : kp_field<float>(kA, q, kY);
           walk(g, cx, cy, cstart, keys, sxy, [&](int i2) { if (k < kend && k < tot) cand[k] = (uint32_t)i2; k++; });
         }
       }
@@ -316,7 +267,7 @@ __global__ __launch_bounds__(kThreads) void k_init_pairs(Args g) {
             for (int j = lane; j < n; j += 64) {
               const uint32_t e = cand[b0 + j];
               const int i2 = (int)(e & 0xFFFFu), d = (int)(e >> 16);
-              if (ld_state(mdist + i2) <= d) continue;
+              if (ld(mdist + i2) <= d) continue;
               if (d < best) { second = best; best = d; pos = j; ibest = i2; }
               else if (d < second) second = d;
             }
@@ -328,12 +279,12 @@ __global__ __launch_bounds__(kThreads) void k_init_pairs(Args g) {
             if ((float)m < (float)d2 * g.ratio) {
               if (win) {
                 const int q = c0 + i;
-                const int was = ld_state(holder + ibest);
-                if (was >= 0) st_state(m12 + was, -1);
-                st_state(m12 + q, ibest);
-                st_state(acc + q, ibest);
-                st_state(holder + ibest, q);
-                st_state(mdist + ibest, m);
+                const int was = ld(holder + ibest);
+                if (was >= 0) st(m12 + was, -1);
+                st(m12 + q, ibest);
+                st(acc + q, ibest);
+                st(holder + ibest, q);
+                st(mdist + ibest, m);
               }
               __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // the stores are done before the next query's loads
             }
@@ -351,7 +302,7 @@ __global__ __launch_bounds__(kThreads) void k_init_pairs(Args g) {
       for (int q = tid; q < nA; q += kThreads) {
         const int v = acc[q];
         if (v >= 0) {
-          const int bin = rot_bin(kp_f(kA, q, kAngle), kp_f(kB, v, kAngle));
+          const int bin = rot_bin(kp_field<float>(kA, q, kAngle), kp_field<float>(kB, v, kAngle));
           if (bin >= 0) atomicAdd(&s_hist[bin], 1);
         }
       }
@@ -379,7 +330,7 @@ __global__ __launch_bounds__(kThreads) void k_init_pairs(Args g) {
       if (q < nA) {
         v = m12[q];
         if (v >= 0 && g.check_ori) {       // a standing match is the one the query was accepted with: its bin is the recorded one
-          const int bin = rot_bin(kp_f(kA, q, kAngle), kp_f(kB, v, kAngle));
+          const int bin = rot_bin(kp_field<float>(kA, q, kAngle), kp_field<float>(kB, v, kAngle));
           if (bin >= 0 && bin != i1 && bin != i2 && bin != i3) v = -1;
         }
         if (v < 0 || v >= nB) v = -1;
@@ -387,7 +338,7 @@ __global__ __launch_bounds__(kThreads) void k_init_pairs(Args g) {
       o12[q] = v;
       if (v >= 0) {
         if (o21) o21[v] = q;
-        if (prev) { prev[2 * q] = kp_f(kB, v, kX); prev[2 * q + 1] = kp_f(kB, v, kY); }
+        if (prev) { prev[2 * q] = kp_field<float>(kB, v, kX); prev[2 * q + 1] = kp_field<float>(kB, v, kY); }
         cnt++;
       }
     }
@@ -401,17 +352,11 @@ __global__ __launch_bounds__(kThreads) void k_init_pairs(Args g) {
 
 struct orbx_initmatch : orbx::side::Handle {   // scratch: per workgroup the global path's arrays
   int lds_limit = kLdsMax;                     // ORBX_INITMATCH_LDS at create
-  std::vector<uint8_t> h_io;                   // the host form's results before they are handed out
 };
 
 namespace {
 
 using namespace orbx::side;
-
-struct HostLayout {                            // offsets in one block, 256-byte aligned
-  size_t size = 0;
-  size_t add(size_t bytes) { const size_t o = size; size = (size + bytes + 255) & ~(size_t)255; return o; }
-};
 
 const char* side_problem(const orbx_initmatch_side* s) {
   if (!s) return "null side";
@@ -445,12 +390,9 @@ int orbx_initmatch_create(orbx_initmatch** out, int device) {
   if (!out) return create_fail(ORBX_E_INVALID, "orbx_initmatch_create", "null argument");
   if (device < 0) return create_fail(ORBX_E_INVALID, "orbx_initmatch_create", "device must be >= 0");
   orbx_initmatch* m = new orbx_initmatch();
-  if (const char* e = std::getenv("ORBX_INITMATCH_LDS")) m->lds_limit = std::max(0, std::min(kLdsMax, std::atoi(e)));
+  m->lds_limit = env_int("ORBX_INITMATCH_LDS", 0, kLdsMax, kLdsMax);
   const char* e = open_handle(m, device);
-  if (!e && hipFuncSetAttribute((const void*)k_init_pairs<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax) != hipSuccess) {
-    (void)hipGetLastError();
-    e = "the kernel's LDS size was refused";
-  }
+  if (!e) e = allow_lds((const void*)k_init_pairs<true>, kLdsMax);
   if (e) { orbx_initmatch_destroy(m); return create_fail(ORBX_E_DEVICE, "orbx_initmatch_create", e); }
   *out = m;
   return ORBX_OK;
@@ -471,13 +413,9 @@ int orbx_initmatch_pairs_device(orbx_initmatch* m, const orbx_initmatch_side* a,
   const char* who = "orbx_initmatch_pairs_device: ";
   int rc = check_call(m, who, a, b, d_pairs, npairs, bounds, window_size, d_matches12, d_nmatches);
   if (rc != ORBX_OK) return rc;
-  for (const void* p : {(const void*)a->d_kps, (const void*)a->d_desc, (const void*)a->d_counts, (const void*)b->d_kps, (const void*)b->d_desc,
-                        (const void*)b->d_counts, (const void*)d_pairs, (const void*)d_prev_xy, (const void*)d_matches12, (const void*)d_matches21,
-                        (const void*)d_nmatches}) {
-    const int pd = pointer_device(p);
-    if (pd >= 0 && pd != m->device)
-      return fail(m, ORBX_E_INVALID, std::string(who) + "a buffer lives on device " + std::to_string(pd) + ", the handle on device " + std::to_string(m->device));
-  }
+  rc = same_device(m, who, {a->d_kps, a->d_desc, a->d_counts, b->d_kps, b->d_desc, b->d_counts, d_pairs, d_prev_xy, d_matches12, d_matches21, d_nmatches},
+                   "the handle");
+  if (rc != ORBX_OK) return rc;
   ORBX_SIDE_HIP(m, hipSetDevice(m->device));
   const int capA = a->capacity, capB = b->capacity;
   int p2 = 2;
@@ -523,49 +461,28 @@ int orbx_initmatch_pairs(orbx_initmatch* m, const orbx_initmatch_side* a, const 
   int rc = check_call(m, who, a, b, pairs, npairs, bounds, window_size, matches12, nmatches);
   if (rc != ORBX_OK) return rc;
   const bool same = a == b || std::memcmp(a, b, sizeof(*a)) == 0;   // one batch on both sides is staged once
-  HostLayout io;
+  Stager io;
   struct Off { size_t kps, desc, counts; } off[2];
   const orbx_initmatch_side* sides[2] = {a, b};
   for (int s = 0; s < (same ? 1 : 2); s++) {
-    const size_t nf = (size_t)sides[s]->nframes, nk = nf * sides[s]->capacity;
-    off[s] = {io.add(nk * sizeof(orbx_keypoint)), io.add(nk * 32), io.add(nf * 8)};
+    const orbx_initmatch_side* h = sides[s];
+    const size_t nf = (size_t)h->nframes, nk = nf * h->capacity;
+    off[s] = {io.in(h->d_kps, nk * sizeof(orbx_keypoint)), io.in(h->d_desc, nk * 32), io.in(h->d_counts, nf * 8)};
   }
   if (same) off[1] = off[0];
-  const size_t o_pairs = io.add((size_t)npairs * 8);
+  const size_t o_pairs = io.in(pairs, (size_t)npairs * 8);
   const size_t n12 = (size_t)npairs * a->capacity * 4, n21 = (size_t)npairs * b->capacity * 4, nprev = prev_xy ? n12 * 2 : 0;
-  const size_t o_out = io.size;                // the results, read back in one copy
-  const size_t o_prev = io.add(nprev), o_12 = io.add(n12), o_21 = io.add(n21), o_nm = io.add((size_t)npairs * 4);
-  ORBX_SIDE_HIP(m, hipSetDevice(m->device));
-  if ((rc = grow(m, &m->io, io.size)) != ORBX_OK) return rc;
-  if (m->h_io.size() < io.size - o_out) m->h_io.resize(io.size - o_out);
+  const size_t o_prev = io.out(prev_xy, nprev, true), o_12 = io.out(matches12, n12), o_21 = io.out(matches21, n21),
+               o_nm = io.out(nmatches, (size_t)npairs * 4);
+  if ((rc = upload(m, io)) != ORBX_OK) return rc;
   uint8_t* d = m->io.p;
-  hipStream_t st = m->st;
-  if ((rc = wait_previous(m, st)) != ORBX_OK) return rc;
   orbx_initmatch_side ds[2];
-  for (int s = 0; s < 2; s++) {
-    const orbx_initmatch_side* h = sides[s];
-    const Off& o = off[s];
-    const size_t nf = (size_t)h->nframes, nk = nf * h->capacity;
-    if (s == 0 || !same) {
-      ORBX_SIDE_HIP(m, hipMemcpyAsync(d + o.kps, h->d_kps, nk * sizeof(orbx_keypoint), hipMemcpyHostToDevice, st));
-      ORBX_SIDE_HIP(m, hipMemcpyAsync(d + o.desc, h->d_desc, nk * 32, hipMemcpyHostToDevice, st));
-      ORBX_SIDE_HIP(m, hipMemcpyAsync(d + o.counts, h->d_counts, nf * 8, hipMemcpyHostToDevice, st));
-    }
-    ds[s] = {(const orbx_keypoint*)(d + o.kps), d + o.desc, (const int32_t*)(d + o.counts), h->nframes, h->capacity};
-  }
-  ORBX_SIDE_HIP(m, hipMemcpyAsync(d + o_pairs, pairs, (size_t)npairs * 8, hipMemcpyHostToDevice, st));
-  if (prev_xy) ORBX_SIDE_HIP(m, hipMemcpyAsync(d + o_prev, prev_xy, nprev, hipMemcpyHostToDevice, st));
+  for (int s = 0; s < 2; s++)
+    ds[s] = {(const orbx_keypoint*)(d + off[s].kps), d + off[s].desc, (const int32_t*)(d + off[s].counts), sides[s]->nframes, sides[s]->capacity};
   rc = orbx_initmatch_pairs_device(m, &ds[0], &ds[1], (const int32_t*)(d + o_pairs), npairs, bounds, window_size, nn_ratio, check_orientation,
-                                   prev_xy ? (float*)(d + o_prev) : nullptr, (int32_t*)(d + o_12), (int32_t*)(d + o_21), (int32_t*)(d + o_nm), st);
+                                   prev_xy ? (float*)(d + o_prev) : nullptr, (int32_t*)(d + o_12), (int32_t*)(d + o_21), (int32_t*)(d + o_nm), m->st);
   if (rc != ORBX_OK) return rc;
-  uint8_t* h = m->h_io.data();
-  ORBX_SIDE_HIP(m, hipMemcpyAsync(h, d + o_out, io.size - o_out, hipMemcpyDeviceToHost, st));
-  if ((rc = finish_host(m)) != ORBX_OK) return rc;
-  if (prev_xy) std::memcpy(prev_xy, h + o_prev - o_out, nprev);
-  std::memcpy(matches12, h + o_12 - o_out, n12);
-  if (matches21) std::memcpy(matches21, h + o_21 - o_out, n21);
-  std::memcpy(nmatches, h + o_nm - o_out, (size_t)npairs * 4);
-  return ORBX_OK;
+  return download(m, io);
 }
 
 }  // extern "C"

@@ -22,15 +22,16 @@
 
 #include <algorithm>
 #include <climits>
-#include <cstdlib>
 #include <cstring>
 #include <string>
-#include <vector>
 
 #include "../side/orbx_handle.h"
+#include "../side/orbx_pair_device.h"
 #include "../../../include/orbx_match.h"
 
 namespace {
+
+using namespace orbx::side::dev;           // ld / st on B's match row: written by one lane, read by the wave's other lanes in the next step
 
 constexpr int kThreads = 512;             // 8 waves
 constexpr int kLdsMax = 152 * 1024;       // dynamic LDS of one workgroup (160 KiB per CU, the static part is below 1 KiB)
@@ -52,64 +53,14 @@ struct Args {
   float ratio;
 };
 
-struct D8 { uint32_t w[8]; };
-
-__device__ __forceinline__ D8 load_desc(const uint8_t* p) {
-  const uint4 x = ((const uint4*)p)[0], y = ((const uint4*)p)[1];
-  D8 d;
-  d.w[0] = x.x; d.w[1] = x.y; d.w[2] = x.z; d.w[3] = x.w; d.w[4] = y.x; d.w[5] = y.y; d.w[6] = y.z; d.w[7] = y.w;
-  return d;
-}
-__device__ __forceinline__ int hamming(const D8& a, const D8& b) {
-  int s = 0;
-#pragma unroll
-  for (int k = 0; k < 8; k++) s += __popc(a.w[k] ^ b.w[k]);
-  return s;
-}
-
-// the minimum over the 64 lanes (all active), wave-uniform: four DPP steps leave each row of 16 lanes with its minimum (lane <-> lane ^ 1,
-// lane ^ 2, mirror of the half row, mirror of the row), the four rows meet through readlane
-__device__ __forceinline__ int wave_min(int v) {
-  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xF, 0xF, false));    // quad_perm [1, 0, 3, 2]
-  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x4E, 0xF, 0xF, false));    // quad_perm [2, 3, 0, 1]
-  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x141, 0xF, 0xF, false));   // row_half_mirror
-  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x140, 0xF, 0xF, false));   // row_mirror
-  return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
-             min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
-}
-
-// B's match row is written by one lane and read by the wave's other lanes in the next step of the same chain
-__device__ __forceinline__ int ld_match(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-__device__ __forceinline__ void st_match(int32_t* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
-// the rotation histogram's bin of a match (src/ORBmatcher.cc:302-311), -1 when it falls outside the 30 bins (then the match is never removed)
-__device__ __forceinline__ int rot_bin(float angle_a, float angle_b) {
-  float rot = angle_a - angle_b;
-  if (rot < 0.0f) rot += 360.0f;
-  const float r = roundf(rot * (1.0f / 30));
-  if (!(r >= 0.0f && r <= 30.0f)) return -1;
-  const int bin = (int)r;
-  return bin == 30 ? 0 : bin;
-}
-__device__ __forceinline__ float kp_angle(const uint8_t* kps, size_t i) { return *(const float*)(kps + i * sizeof(orbx_keypoint) + offsetof(orbx_keypoint, angle)); }
+constexpr size_t kAngle = offsetof(orbx_keypoint, angle);
 
 __device__ __forceinline__ void fail_rows(const Args& g, int p, int32_t* ob, int32_t* oa) {
   if (ob) for (int i = threadIdx.x; i < g.b.cap; i += kThreads) ob[i] = -1;
   if (oa) for (int i = threadIdx.x; i < g.a.cap; i += kThreads) oa[i] = -1;
   if (threadIdx.x == 0) g.nm[p] = -1;
-}
-
-// n16 16-byte pieces from src to the LDS block at dst: piece i lands at dst + 16 i (lane-linear inside a wave, as the LDS-DMA load writes)
-__device__ __forceinline__ void stage_dma(uint8_t* dst, const uint8_t* src, int n16) {
-  for (int i0 = 0; i0 < n16; i0 += kThreads) {
-    const int i = i0 + (int)threadIdx.x;
-    uint8_t* d = dst + (size_t)(i0 + ((int)threadIdx.x & ~63)) * 16;   // wave-uniform; the hardware adds lane * 16
-    if (i < n16)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (size_t)i * 16),
-                                       (__attribute__((address_space(3))) void*)d, 16, 0, 0);
-  }
 }
 
 template <bool LDS>
@@ -163,8 +114,8 @@ __global__ __launch_bounds__(kThreads) void k_match_pairs(Args g) {
     if (tid == 0) { s_cnt = 0; s_next = 0; s_bad = 0; s_nm = 0; }
     if (tid < 32) s_hist[tid] = 0;
     if (LDS) {
-      stage_dma(l_dA, g.a.desc + oA * 32, nA * 2);
-      stage_dma(l_dB, g.b.desc + oB * 32, nB * 2);
+      stage_dma<kThreads>(l_dA, g.a.desc + oA * 32, nA * 2);
+      stage_dma<kThreads>(l_dB, g.b.desc + oB * 32, nB * 2);
     }
     __syncthreads();                       // s_bad = 0 before anyone raises it
     for (int i = tid; i < totA; i += kThreads) {
@@ -225,7 +176,7 @@ __global__ __launch_bounds__(kThreads) void k_match_pairs(Args g) {
       for (int k = 0; k < 8; k++) my_db.w[k] = 0;
       if (regs && lane < nb) {
         my_fb = fB[b0 + lane];
-        my_free = ld_match(match + my_fb) == -1;
+        my_free = ld(match + my_fb) == -1;
         my_db = load_desc(dB + (size_t)my_fb * 32);
       }
       for (int c0 = 0; c0 < na; c0 += 64) {
@@ -246,14 +197,14 @@ __global__ __launch_bounds__(kThreads) void k_match_pairs(Args g) {
             const int win = __ffsll((long long)__ballot(d == m)) - 1;   // candidates lie in list order over the lanes: the first minimum
             const int d2 = wave_min(lane == win ? 256 : d);
             if ((float)m < g.ratio * (float)d2) {
-              if (lane == win) { my_free = false; st_match(match + my_fb, fa); }
+              if (lane == win) { my_free = false; st(match + my_fb, fa); }
             }
           } else {
             int best = 256, second = 256, pos = INT_MAX;
             uint32_t fbest = 0;
             for (int j = lane; j < nb; j += 64) {
               const uint32_t fb = fB[b0 + j];
-              if (ld_match(match + fb) != -1) continue;
+              if (ld(match + fb) != -1) continue;
               const int d = hamming(da, load_desc(dB + (size_t)fb * 32));
               if (d < best) { second = best; best = d; pos = j; fbest = fb; }
               else if (d < second) second = d;
@@ -264,7 +215,7 @@ __global__ __launch_bounds__(kThreads) void k_match_pairs(Args g) {
             const bool win = best == m && pos == wpos;
             const int d2 = wave_min(win ? second : best);
             if ((float)m < g.ratio * (float)d2) {
-              if (win) st_match(match + fbest, fa);
+              if (win) st(match + fbest, fa);
               __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // the store is done before the next A feature's loads
             }
           }
@@ -279,7 +230,7 @@ __global__ __launch_bounds__(kThreads) void k_match_pairs(Args g) {
       for (int b = tid; b < nB; b += kThreads) {
         const int m = match[b];
         if (m >= 0) {
-          const int bin = rot_bin(kp_angle(g.a.kps, oA + m), kp_angle(g.b.kps, oB + b));
+          const int bin = rot_bin(kp_field<float>(g.a.kps, oA + m, kAngle), kp_field<float>(g.b.kps, oB + b, kAngle));
           if (bin >= 0) atomicAdd(&s_hist[bin], 1);
         }
       }
@@ -305,7 +256,7 @@ __global__ __launch_bounds__(kThreads) void k_match_pairs(Args g) {
       if (b < nB) {
         v = match[b];
         if (v >= 0 && g.check_ori) {
-          const int bin = rot_bin(kp_angle(g.a.kps, oA + v), kp_angle(g.b.kps, oB + b));
+          const int bin = rot_bin(kp_field<float>(g.a.kps, oA + v, kAngle), kp_field<float>(g.b.kps, oB + b, kAngle));
           if (bin >= 0 && bin != i1 && bin != i2 && bin != i3) v = -1;
         }
         if (v < 0) v = -1;
@@ -327,17 +278,11 @@ __global__ __launch_bounds__(kThreads) void k_match_pairs(Args g) {
 struct orbx_match : orbx::side::Handle {   // scratch: per workgroup the global path's work list and match row
   int lds_limit = kLdsMax;                 // ORBX_MATCH_LDS at create
   int wave_node = kWaveNode;               // ORBX_MATCH_WAVE_NODE at create
-  std::vector<uint8_t> h_io;               // the host form's results before they are handed out
 };
 
 namespace {
 
 using namespace orbx::side;
-
-struct Layout {                            // offsets in one block, 256-byte aligned
-  size_t size = 0;
-  size_t add(size_t bytes) { const size_t o = size; size = (size + bytes + 255) & ~(size_t)255; return o; }
-};
 
 const char* side_problem(const orbx_match_side* s) {
   if (!s) return "null side";
@@ -374,13 +319,10 @@ int orbx_match_create(orbx_match** out, int device) {
   if (!out) return create_fail(ORBX_E_INVALID, "orbx_match_create", "null argument");
   if (device < 0) return create_fail(ORBX_E_INVALID, "orbx_match_create", "device must be >= 0");
   orbx_match* m = new orbx_match();
-  if (const char* e = std::getenv("ORBX_MATCH_LDS")) m->lds_limit = std::max(0, std::min(kLdsMax, std::atoi(e)));
-  if (const char* e = std::getenv("ORBX_MATCH_WAVE_NODE")) m->wave_node = std::max(0, std::min(kWaveNode, std::atoi(e)));
+  m->lds_limit = env_int("ORBX_MATCH_LDS", 0, kLdsMax, kLdsMax);
+  m->wave_node = env_int("ORBX_MATCH_WAVE_NODE", 0, kWaveNode, kWaveNode);
   const char* e = open_handle(m, device);
-  if (!e && hipFuncSetAttribute((const void*)k_match_pairs<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax) != hipSuccess) {
-    (void)hipGetLastError();
-    e = "the kernel's LDS size was refused";
-  }
+  if (!e) e = allow_lds((const void*)k_match_pairs<true>, kLdsMax);
   if (e) { orbx_match_destroy(m); return create_fail(ORBX_E_DEVICE, "orbx_match_create", e); }
   *out = m;
   return ORBX_OK;
@@ -401,12 +343,8 @@ int orbx_match_bow_pairs_device(orbx_match* m, const orbx_match_side* a, const o
   const char* who = "orbx_match_bow_pairs_device: ";
   int rc = check_call(m, who, a, b, d_pairs, npairs, mode, d_match_b2a, d_match_a2b, d_nmatches);
   if (rc != ORBX_OK) return rc;
-  for (const void* p : {(const void*)a->d_kps, (const void*)a->d_desc, (const void*)a->d_fv_feat, (const void*)b->d_kps, (const void*)b->d_desc,
-                        (const void*)b->d_fv_feat, (const void*)d_pairs, (const void*)d_match_b2a, (const void*)d_match_a2b, (const void*)d_nmatches}) {
-    const int pd = pointer_device(p);
-    if (pd >= 0 && pd != m->device)
-      return fail(m, ORBX_E_INVALID, std::string(who) + "a buffer lives on device " + std::to_string(pd) + ", the handle on device " + std::to_string(m->device));
-  }
+  rc = same_device(m, who, {a->d_kps, a->d_desc, a->d_fv_feat, b->d_kps, b->d_desc, b->d_fv_feat, d_pairs, d_match_b2a, d_match_a2b, d_nmatches}, "the handle");
+  if (rc != ORBX_OK) return rc;
   ORBX_SIDE_HIP(m, hipSetDevice(m->device));
   const size_t capA = (size_t)a->capacity, capB = (size_t)b->capacity, capW = std::min(capA, capB);
   const size_t lds = 32 * (capA + capB) + 16 * capW + 4 * (capB + capA + capB);
@@ -437,53 +375,31 @@ int orbx_match_bow_pairs(orbx_match* m, const orbx_match_side* a, const orbx_mat
   int rc = check_call(m, who, a, b, pairs, npairs, mode, match_b2a, match_a2b, nmatches);
   if (rc != ORBX_OK) return rc;
   const bool same = a == b || std::memcmp(a, b, sizeof(*a)) == 0;   // one batch on both sides is staged once
-  Layout io;
+  Stager io;
   struct Off { size_t kps, desc, counts, node, ptr, feat, n, valid; } off[2];
   const orbx_match_side* sides[2] = {a, b};
   for (int s = 0; s < (same ? 1 : 2); s++) {
-    const size_t nf = (size_t)sides[s]->nframes, nk = nf * sides[s]->capacity;
-    off[s] = {io.add(nk * sizeof(orbx_keypoint)), io.add(nk * 32), io.add(nf * 8), io.add(nk * 4), io.add((nk + nf) * 4), io.add(nk * 4), io.add(nf * 4),
-              sides[s]->d_valid ? io.add(nk) : 0};
+    const orbx_match_side* h = sides[s];
+    const size_t nf = (size_t)h->nframes, nk = nf * h->capacity;
+    off[s] = {io.in(h->d_kps, nk * sizeof(orbx_keypoint)), io.in(h->d_desc, nk * 32), io.in(h->d_counts, nf * 8), io.in(h->d_fv_node, nk * 4),
+              io.in(h->d_fv_ptr, (nk + nf) * 4), io.in(h->d_fv_feat, nk * 4), io.in(h->d_fv_n, nf * 4), h->d_valid ? io.in(h->d_valid, nk) : 0};
   }
   if (same) off[1] = off[0];
-  const size_t o_pairs = io.add((size_t)npairs * 8);
-  const size_t o_out = io.size;            // the results, read back in one copy
-  const size_t o_b2a = io.add((size_t)npairs * b->capacity * 4), o_a2b = io.add((size_t)npairs * a->capacity * 4), o_nm = io.add((size_t)npairs * 4);
-  ORBX_SIDE_HIP(m, hipSetDevice(m->device));
-  if ((rc = grow(m, &m->io, io.size)) != ORBX_OK) return rc;
-  if (m->h_io.size() < io.size - o_out) m->h_io.resize(io.size - o_out);
+  const size_t o_pairs = io.in(pairs, (size_t)npairs * 8);
+  const size_t o_b2a = io.out(match_b2a, (size_t)npairs * b->capacity * 4), o_a2b = io.out(match_a2b, (size_t)npairs * a->capacity * 4),
+               o_nm = io.out(nmatches, (size_t)npairs * 4);
+  if ((rc = upload(m, io)) != ORBX_OK) return rc;
   uint8_t* d = m->io.p;
-  hipStream_t st = m->st;
-  if ((rc = wait_previous(m, st)) != ORBX_OK) return rc;
   orbx_match_side ds[2];
   for (int s = 0; s < 2; s++) {
-    const orbx_match_side* h = sides[s];
     const Off& o = off[s];
-    const size_t nf = (size_t)h->nframes, nk = nf * h->capacity;
-    if (s == 0 || !same) {
-      ORBX_SIDE_HIP(m, hipMemcpyAsync(d + o.kps, h->d_kps, nk * sizeof(orbx_keypoint), hipMemcpyHostToDevice, st));
-      ORBX_SIDE_HIP(m, hipMemcpyAsync(d + o.desc, h->d_desc, nk * 32, hipMemcpyHostToDevice, st));
-      ORBX_SIDE_HIP(m, hipMemcpyAsync(d + o.counts, h->d_counts, nf * 8, hipMemcpyHostToDevice, st));
-      ORBX_SIDE_HIP(m, hipMemcpyAsync(d + o.node, h->d_fv_node, nk * 4, hipMemcpyHostToDevice, st));
-      ORBX_SIDE_HIP(m, hipMemcpyAsync(d + o.ptr, h->d_fv_ptr, (nk + nf) * 4, hipMemcpyHostToDevice, st));
-      ORBX_SIDE_HIP(m, hipMemcpyAsync(d + o.feat, h->d_fv_feat, nk * 4, hipMemcpyHostToDevice, st));
-      ORBX_SIDE_HIP(m, hipMemcpyAsync(d + o.n, h->d_fv_n, nf * 4, hipMemcpyHostToDevice, st));
-      if (h->d_valid) ORBX_SIDE_HIP(m, hipMemcpyAsync(d + o.valid, h->d_valid, nk, hipMemcpyHostToDevice, st));
-    }
     ds[s] = {(const orbx_keypoint*)(d + o.kps), d + o.desc, (const int32_t*)(d + o.counts), (const uint32_t*)(d + o.node), (const int32_t*)(d + o.ptr),
-             (const uint32_t*)(d + o.feat), (const int32_t*)(d + o.n), h->d_valid ? d + o.valid : nullptr, h->nframes, h->capacity};
+             (const uint32_t*)(d + o.feat), (const int32_t*)(d + o.n), sides[s]->d_valid ? d + o.valid : nullptr, sides[s]->nframes, sides[s]->capacity};
   }
-  ORBX_SIDE_HIP(m, hipMemcpyAsync(d + o_pairs, pairs, (size_t)npairs * 8, hipMemcpyHostToDevice, st));
   rc = orbx_match_bow_pairs_device(m, &ds[0], &ds[1], (const int32_t*)(d + o_pairs), npairs, mode, nn_ratio, check_orientation, (int32_t*)(d + o_b2a),
-                                   (int32_t*)(d + o_a2b), (int32_t*)(d + o_nm), st);
+                                   (int32_t*)(d + o_a2b), (int32_t*)(d + o_nm), m->st);
   if (rc != ORBX_OK) return rc;
-  uint8_t* h = m->h_io.data();
-  ORBX_SIDE_HIP(m, hipMemcpyAsync(h, d + o_out, io.size - o_out, hipMemcpyDeviceToHost, st));
-  if ((rc = finish_host(m)) != ORBX_OK) return rc;
-  if (match_b2a) std::memcpy(match_b2a, h + o_b2a - o_out, (size_t)npairs * b->capacity * 4);
-  if (match_a2b) std::memcpy(match_a2b, h + o_a2b - o_out, (size_t)npairs * a->capacity * 4);
-  std::memcpy(nmatches, h + o_nm - o_out, (size_t)npairs * 4);
-  return ORBX_OK;
+  return download(m, io);
 }
 
 }  // extern "C"

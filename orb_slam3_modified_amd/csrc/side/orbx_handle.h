@@ -1,12 +1,18 @@
-// The host-side core of a side library's handle (liborbx_stereo.so, liborbx_bow.so: DESIGN.md sections 10 and 11).  Host code only; it sits
-// below csrc/, outside kernels_hash().  A handle derives from orbx::side::Handle and adds what is its own.
+// The host-side core of a side library's handle (liborbx_stereo.so, liborbx_bow.so, liborbx_match.so, liborbx_initmatch.so: DESIGN.md
+// sections 10 and 11).  Host code only; it sits below csrc/, outside kernels_hash().  A handle derives from orbx::side::Handle and adds what
+// is its own.  The device helpers of the pair matchers are in orbx_pair_device.h.
 //
 // The rule it keeps: the calls on one handle share its scratch, so each waits for the one before it (wait_previous / record_call around
 // ev_done), and a block of the handle is replaced only once the handle is idle (grow behind quiesce).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <initializer_list>
 #include <string>
+#include <vector>
 
 #include "../../../include/orbx.h"
 
@@ -22,8 +28,20 @@ struct Handle {
   bool pending = false;            // ev_done recorded: the previous call's work may still use the scratch
   Block scratch;                   // the kernels' intermediate buffers
   Block io;                        // the host forms' device copies of arguments and results
+  std::vector<uint8_t> h_io;       // the host forms' results before they are handed out
   std::string err;
 };
+
+struct Layout {                    // offsets in one block, 256-byte aligned
+  size_t size = 0;
+  size_t add(size_t bytes) { const size_t o = size; size = (size + bytes + 255) & ~(size_t)255; return o; }
+};
+
+// an integer from the environment, clamped to [lo, hi]; `fallback` when the variable is not set
+inline int env_int(const char* name, int lo, int hi, int fallback) {
+  const char* e = std::getenv(name);
+  return e ? std::max(lo, std::min(hi, std::atoi(e))) : fallback;
+}
 
 inline thread_local std::string t_create_err;   // why the last create of this thread failed: there is no handle to hold it
 
@@ -90,6 +108,66 @@ inline int pointer_device(const void* p) {
   hipPointerAttribute_t at;
   if (!p || hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return -1; }
   return at.type == hipMemoryTypeDevice ? at.device : -1;
+}
+
+// every buffer the runtime knows lives on the handle's device; `owner` names in the message what the handle's device is that of
+inline int same_device(Handle* h, const char* who, std::initializer_list<const void*> buffers, const char* owner) {
+  for (const void* p : buffers) {
+    const int pd = pointer_device(p);
+    if (pd >= 0 && pd != h->device)
+      return fail(h, ORBX_E_INVALID, std::string(who) + "a buffer lives on device " + std::to_string(pd) + ", " + owner + " on device " + std::to_string(h->device));
+  }
+  return ORBX_OK;
+}
+
+// a kernel may be launched with up to `bytes` of dynamic LDS; what failed, or nullptr
+inline const char* allow_lds(const void* kernel, int bytes) {
+  if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess) return nullptr;
+  (void)hipGetLastError();
+  return "the kernel's LDS size was refused";
+}
+
+// A host form's arguments and results in the handle's io block.  The form declares its inputs, then its results (which lie together at the
+// end of the block), each call returning the offset in the block; upload() queues the inputs' copies in the order of their declaration, the
+// form calls its device form on h->io.p + offset, and download() reads the results back in one copy and hands them out.
+struct Stager {
+  struct Item { size_t off, bytes; const void* src; void* dst; };
+  Layout lay;
+  size_t o_out = 0;                // where the results begin
+  std::vector<Item> ins, outs;
+  size_t in(const void* host, size_t bytes) {
+    const size_t o = lay.add(bytes);
+    ins.push_back({o, bytes, host, nullptr});
+    return o;
+  }
+  // `host` null: the result has its place but is not handed out.  `both`: what `host` holds is uploaded first (an argument that is updated)
+  size_t out(void* host, size_t bytes, bool both = false) {
+    if (outs.empty()) o_out = lay.size;
+    const size_t o = lay.add(bytes);
+    if (both && host) ins.push_back({o, bytes, host, nullptr});
+    outs.push_back({o, bytes, nullptr, host});
+    return o;
+  }
+};
+
+inline int upload(Handle* h, const Stager& s) {
+  ORBX_SIDE_HIP(h, hipSetDevice(h->device));
+  int rc = grow(h, &h->io, s.lay.size);
+  if (rc != ORBX_OK) return rc;
+  if ((rc = wait_previous(h, h->st)) != ORBX_OK) return rc;
+  for (const Stager::Item& i : s.ins) ORBX_SIDE_HIP(h, hipMemcpyAsync(h->io.p + i.off, i.src, i.bytes, hipMemcpyHostToDevice, h->st));
+  return ORBX_OK;
+}
+
+inline int download(Handle* h, const Stager& s) {
+  const size_t bytes = s.lay.size - s.o_out;
+  if (h->h_io.size() < bytes) h->h_io.resize(bytes);
+  ORBX_SIDE_HIP(h, hipMemcpyAsync(h->h_io.data(), h->io.p + s.o_out, bytes, hipMemcpyDeviceToHost, h->st));
+  const int rc = finish_host(h);
+  if (rc != ORBX_OK) return rc;
+  for (const Stager::Item& o : s.outs)
+    if (o.dst) std::memcpy(o.dst, h->h_io.data() + o.off - s.o_out, o.bytes);
+  return ORBX_OK;
 }
 
 // the handle's stream and event on `device`; what failed, or nullptr.  close_handle() takes a half-opened handle too

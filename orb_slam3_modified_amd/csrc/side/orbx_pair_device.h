@@ -1,0 +1,76 @@
+// The device helpers the batched pair matchers share (liborbx_match.so, liborbx_initmatch.so): descriptors and Hamming distances, the wave
+// minimum, a chain's relaxed loads and stores, the rotation bin, the keypoint field reader and the LDS-DMA staging.  Device code only; it
+// sits below csrc/, outside kernels_hash().  A kernel's file imports the names with `using namespace orbx::side::dev;` inside its anonymous
+// namespace.  ComputeThreeMaxima and the trip loop's three-reduction merge stay written out in both kernels: as functions of this header
+// they change the kernels' instruction streams (the compiler unrolls and schedules them differently).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+
+#include "../../../include/orbx.h"
+
+namespace orbx {
+namespace side {
+namespace dev {
+
+struct D8 { uint32_t w[8]; };
+
+__device__ __forceinline__ D8 load_desc(const uint8_t* p) {
+  const uint4 x = ((const uint4*)p)[0], y = ((const uint4*)p)[1];
+  D8 d;
+  d.w[0] = x.x; d.w[1] = x.y; d.w[2] = x.z; d.w[3] = x.w; d.w[4] = y.x; d.w[5] = y.y; d.w[6] = y.z; d.w[7] = y.w;
+  return d;
+}
+__device__ __forceinline__ int hamming(const D8& a, const D8& b) {
+  int s = 0;
+#pragma unroll
+  for (int k = 0; k < 8; k++) s += __popc(a.w[k] ^ b.w[k]);
+  return s;
+}
+
+// the minimum over the 64 lanes (all active), wave-uniform: four DPP steps leave each row of 16 lanes with its minimum (lane <-> lane ^ 1,
+// lane ^ 2, mirror of the half row, mirror of the row), the four rows meet through readlane
+__device__ __forceinline__ int wave_min(int v) {
+  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xF, 0xF, false));    // quad_perm [1, 0, 3, 2]
+  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x4E, 0xF, 0xF, false));    // quad_perm [2, 3, 0, 1]
+  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x141, 0xF, 0xF, false));   // row_half_mirror
+  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x140, 0xF, 0xF, false));   // row_mirror
+  return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
+             min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
+}
+
+// a chain's state is written by one lane and read by the wave's other lanes in the next step of the same chain
+__device__ __forceinline__ int ld(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+__device__ __forceinline__ void st(int32_t* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+
+// the rotation histogram's bin of a match (src/ORBmatcher.cc:302-311, :718-725), -1 when it falls outside the 30 bins (then the match is
+// never removed)
+__device__ __forceinline__ int rot_bin(float angle_a, float angle_b) {
+  float rot = angle_a - angle_b;
+  if (rot < 0.0f) rot += 360.0f;
+  const float r = roundf(rot * (1.0f / 30));
+  if (!(r >= 0.0f && r <= 30.0f)) return -1;
+  const int bin = (int)r;
+  return bin == 30 ? 0 : bin;
+}
+
+// field `field` (an offsetof) of keypoint i of a keypoint array
+template <class T>
+__device__ __forceinline__ T kp_field(const uint8_t* kps, size_t i, size_t field) { return *(const T*)(kps + i * sizeof(orbx_keypoint) + field); }
+
+// n16 16-byte pieces from src to the LDS block at dst: piece i lands at dst + 16 i (lane-linear inside a wave, as the LDS-DMA load writes)
+template <int THREADS>
+__device__ __forceinline__ void stage_dma(uint8_t* dst, const uint8_t* src, int n16) {
+  for (int i0 = 0; i0 < n16; i0 += THREADS) {
+    const int i = i0 + (int)threadIdx.x;
+    uint8_t* d = dst + (size_t)(i0 + ((int)threadIdx.x & ~63)) * 16;   // wave-uniform; the hardware adds lane * 16
+    if (i < n16)
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (size_t)i * 16),
+                                       (__attribute__((address_space(3))) void*)d, 16, 0, 0);
+  }
+}
+
+}  // namespace dev
+}  // namespace side
+}  // namespace orbx

@@ -10,8 +10,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._lib import KP_DTYPE, OrbxInitMatchSide, ptr
-from .match import _addr
+from ._lib import KP_DTYPE, OrbxInitMatchSide, addr, host_array as arr, host_view, ptr
 
 LDS_MAX = 152 * 1024     # the largest LDS block of a workgroup (ORBX_INITMATCH_LDS lowers it)
 MAX_CAPACITY = 32768
@@ -38,15 +37,14 @@ class InitSide:
     capacity: int
 
     def _struct(self) -> OrbxInitMatchSide:
-        return OrbxInitMatchSide(*(_addr(t) or None for t in (self.kps, self.desc, self.counts)), int(self.nframes), int(self.capacity))
+        return OrbxInitMatchSide(*(addr(t) or None for t in (self.kps, self.desc, self.counts)), int(self.nframes), int(self.capacity))
 
     def _host(self) -> "InitSide":
         """Contiguous numpy arrays of the ABI's element types."""
         F, cap = int(self.nframes), int(self.capacity)
         kps = np.ascontiguousarray(self.kps)
         assert kps.nbytes == F * cap * KP_DTYPE.itemsize
-        return InitSide(kps, np.ascontiguousarray(self.desc, np.uint8).reshape(F, cap, 32), np.ascontiguousarray(self.counts, np.int32).reshape(F, 2),
-                        F, cap)
+        return InitSide(kps, arr(self.desc, np.uint8, F, cap, 32), arr(self.counts, np.int32, F, 2), F, cap)
 
 
 @dataclass
@@ -63,9 +61,7 @@ class InitResult:
         return int(self.nmatches.shape[0])
 
     def __getitem__(self, p: int):
-        h = lambda t: None if t is None else (t if isinstance(t, np.ndarray) else t.cpu().numpy())   # noqa: E731
-        n = h(self.nmatches[p:p + 1])
-        return int(n[0]), h(self.matches12[p]), h(None if self.matches21 is None else self.matches21[p])
+        return int(host_view(self.nmatches[p:p + 1])[0]), *(None if t is None else host_view(t[p]) for t in (self.matches12, self.matches21))
 
 
 class InitMatchBatch(_lib.SideHandle):
@@ -90,9 +86,9 @@ class InitMatchBatch(_lib.SideHandle):
         out.prev_xy = prev_xy
         sa, sb = a._struct(), b._struct()
         bd = (C.c_float * 4)(*[float(v) for v in bounds])
-        self._check(self._M.orbx_initmatch_pairs_device(self._h, C.byref(sa), C.byref(sb), ptr(_addr(pairs)), P, bd, int(window_size),
-                                                        float(nn_ratio), int(bool(check_orientation)), ptr(_addr(prev_xy)),
-                                                        ptr(_addr(out.matches12)), ptr(_addr(out.matches21)), ptr(_addr(out.nmatches)),
+        self._check(self._M.orbx_initmatch_pairs_device(self._h, C.byref(sa), C.byref(sb), ptr(addr(pairs)), P, bd, int(window_size),
+                                                        float(nn_ratio), int(bool(check_orientation)), ptr(addr(prev_xy)),
+                                                        ptr(addr(out.matches12)), ptr(addr(out.matches21)), ptr(addr(out.nmatches)),
                                                         ptr(int(stream or 0))))
         return out
 

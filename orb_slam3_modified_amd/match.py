@@ -10,18 +10,9 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._lib import KP_DTYPE, OrbxMatchSide, ptr
+from ._lib import KP_DTYPE, OrbxMatchSide, addr, host_array as arr, host_view, ptr
 
 FRAME, KEYFRAMES = 0, 1   # ORBX_MATCH_FRAME, ORBX_MATCH_KEYFRAMES
-
-
-def _addr(t) -> int:
-    """An address: a torch tensor's data_ptr(), a numpy array's buffer, an int, or None (0)."""
-    if t is None:
-        return 0
-    if isinstance(t, np.ndarray):
-        return int(t.ctypes.data)
-    return int(t.data_ptr()) if hasattr(t, "data_ptr") else int(t)
 
 
 @dataclass
@@ -46,7 +37,7 @@ class MatchSide:
         return cls(kps, desc, counts, fv.fv_node, fv.fv_ptr, fv.fv_feat, fv.fv_n, int(nframes), int(capacity), valid)
 
     def _struct(self) -> OrbxMatchSide:
-        return OrbxMatchSide(*(_addr(t) or None for t in (self.kps, self.desc, self.counts, self.fv_node, self.fv_ptr, self.fv_feat, self.fv_n,
+        return OrbxMatchSide(*(addr(t) or None for t in (self.kps, self.desc, self.counts, self.fv_node, self.fv_ptr, self.fv_feat, self.fv_n,
                                                            self.valid)), int(self.nframes), int(self.capacity))
 
     def _host(self) -> "MatchSide":
@@ -54,10 +45,9 @@ class MatchSide:
         F, cap = int(self.nframes), int(self.capacity)
         kps = np.ascontiguousarray(self.kps)
         assert kps.nbytes == F * cap * KP_DTYPE.itemsize
-        a = lambda x, dt, *shape: np.ascontiguousarray(x, dt).reshape(shape)   # noqa: E731
-        return MatchSide(kps, a(self.desc, np.uint8, F, cap, 32), a(self.counts, np.int32, F, 2), a(self.fv_node, np.uint32, F, cap),
-                         a(self.fv_ptr, np.int32, F, cap + 1), a(self.fv_feat, np.uint32, F, cap), a(self.fv_n, np.int32, F), F, cap,
-                         None if self.valid is None else a(self.valid, np.uint8, F, cap))
+        return MatchSide(kps, arr(self.desc, np.uint8, F, cap, 32), arr(self.counts, np.int32, F, 2), arr(self.fv_node, np.uint32, F, cap),
+                         arr(self.fv_ptr, np.int32, F, cap + 1), arr(self.fv_feat, np.uint32, F, cap), arr(self.fv_n, np.int32, F), F, cap,
+                         None if self.valid is None else arr(self.valid, np.uint8, F, cap))
 
 
 @dataclass
@@ -72,9 +62,7 @@ class MatchResult:
         return int(self.nmatches.shape[0])
 
     def __getitem__(self, p: int):
-        h = lambda t: None if t is None else (t if isinstance(t, np.ndarray) else t.cpu().numpy())   # noqa: E731
-        n, b, a = h(self.nmatches[p:p + 1]), h(None if self.b2a is None else self.b2a[p]), h(None if self.a2b is None else self.a2b[p])
-        return int(n[0]), b, a
+        return int(host_view(self.nmatches[p:p + 1])[0]), *(None if t is None else host_view(t[p]) for t in (self.b2a, self.a2b))
 
 
 class MatchBatch(_lib.SideHandle):
@@ -96,9 +84,9 @@ class MatchBatch(_lib.SideHandle):
             out = MatchResult(torch.empty(P, dtype=torch.int32, device=dev), torch.empty((P, b.capacity), dtype=torch.int32, device=dev),
                               torch.empty((P, a.capacity), dtype=torch.int32, device=dev))
         sa, sb = a._struct(), b._struct()
-        self._check(self._M.orbx_match_bow_pairs_device(self._h, C.byref(sa), C.byref(sb), ptr(_addr(pairs)), P, int(mode), float(nn_ratio),
-                                                        int(bool(check_orientation)), ptr(_addr(out.b2a)), ptr(_addr(out.a2b)),
-                                                        ptr(_addr(out.nmatches)), ptr(int(stream or 0))))
+        self._check(self._M.orbx_match_bow_pairs_device(self._h, C.byref(sa), C.byref(sb), ptr(addr(pairs)), P, int(mode), float(nn_ratio),
+                                                        int(bool(check_orientation)), ptr(addr(out.b2a)), ptr(addr(out.a2b)),
+                                                        ptr(addr(out.nmatches)), ptr(int(stream or 0))))
         return out
 
     def bow_pairs(self, a: MatchSide, b: MatchSide, pairs, mode: int = FRAME, nn_ratio: float = 0.7, check_orientation: bool = True) -> MatchResult:

@@ -22,6 +22,13 @@ def declared(header: str = "orbx.h") -> list:
     return sorted(set(re.findall(r"\b(orbx_[a-z0-9_]+)\s*\(", h)))
 
 
+def struct_fields(header: str, name: str) -> list:
+    """The field names of `typedef struct <name> { ... } <name>;` in include/<header>, in order."""
+    h = open(os.path.join(ROOT, "include", header)).read()
+    body = re.sub(r"/\*.*?\*/", "", h[h.index("typedef struct %s {" % name):h.index("} %s;" % name)], flags=re.S)
+    return [n for decl in re.findall(r"([^;{]+);", body) for n in re.findall(r"\b(\w+)\s*(?:,|$)", decl.strip())]
+
+
 def exported(path: str) -> set:
     """The functions a shared library defines and exports."""
     out = subprocess.check_output(["nm", "-D", "--defined-only", path]).decode()

@@ -8,7 +8,6 @@ import pytest
 
 from oracle import pyoracle as po
 from orb_slam3_modified_amd import ORBextractor, ORBmatcher, ORBVocabulary, OrbxError, _lib, synth
-from orb_slam3_modified_amd._lib import KP_DTYPE
 from orb_slam3_modified_amd.bow import BowBatch
 from orb_slam3_modified_amd.match import FRAME, KEYFRAMES, MatchBatch, MatchSide
 from tests import match_batch_model as mm
@@ -17,31 +16,14 @@ from tests.vocab_util import make_vocabulary
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-EUROC = (480, 752, (1000, 1.2, 8, 20, 7))
-VGA5K = (480, 640, (5000, 1.2, 8, 20, 7))
+from tests.pair_batch_util import EUROC, VGA5K, Batch as HbmBatch, dev, pairs256  # noqa: E402
 
 
-def _dev():
-    return torch.device("cuda", 0)
-
-
-class Batch:
-    """B frames extracted into HBM, their host copies, and per levelsup the FeatureVectors (device result + host dicts)."""
+class Batch(HbmBatch):
+    """The extracted frames and, per levelsup, their FeatureVectors (device result + host dicts)."""
 
     def __init__(self, ex, imgs):
-        B, H, W = imgs.shape
-        self.ex, self.B, self.cap = ex, B, ex.capacity
-        self.s = torch.cuda.Stream(device=_dev())
-        t = torch.from_numpy(np.ascontiguousarray(imgs)).to(_dev())
-        self.kps = torch.zeros((B, self.cap, 28), dtype=torch.uint8, device=_dev())
-        self.desc = torch.zeros((B, self.cap, 32), dtype=torch.uint8, device=_dev())
-        self.counts = torch.zeros((B, 2), dtype=torch.int32, device=_dev())
-        torch.cuda.synchronize()
-        ex.extract_batch_device(t.data_ptr(), B, H, W, W, H * W, self.kps.data_ptr(), self.desc.data_ptr(), self.counts.data_ptr(), (0, 1000),
-                                stream=self.s.cuda_stream)
-        self.s.synchronize()
-        self.hk = self.kps.cpu().numpy().view(KP_DTYPE).reshape(B, self.cap)
-        self.hd, self.hc = self.desc.cpu().numpy(), self.counts.cpu().numpy()
+        super().__init__(ex, imgs)
         self.fv, self.hfv = {}, {}
 
     def transform(self, gv, key, levelsup):
@@ -61,10 +43,6 @@ class Batch:
         hi = self.B if hi is None else hi
         return MatchSide(self.kps[lo:hi], self.desc[lo:hi], self.counts[lo:hi], fv.fv_node[lo:hi], fv.fv_ptr[lo:hi], fv.fv_feat[lo:hi], fv.fv_n[lo:hi],
                          hi - lo, self.cap, None if valid is None else valid[lo:hi])
-
-    def frame(self, f):
-        n = int(self.hc[f, 0])
-        return self.hd[f, :n], self.hk[f, :n]["angle"]
 
 
 def _voc(ex, tmp_path_factory, train, k, L, seed):
@@ -88,19 +66,11 @@ def euroc(tmp_path_factory):
 def _mask(bt, seed, frac=0.7):
     rng = np.random.default_rng(seed)
     hv = (rng.random((bt.B, bt.cap)) < frac).astype(np.uint8)
-    return torch.from_numpy(hv).to(_dev()), hv
-
-
-def _pairs256():
-    """200 x (f, f + 1), 24 x (f, f + 5), 8 x (f, f), frame 7 against 24 others."""
-    p = [(f, f + 1) for f in range(200)] + [(f, f + 5) for f in range(0, 240, 10)] + [(f, f) for f in range(3, 256, 32)]
-    p += [(7, g) for g in range(8, 32)]
-    assert len(p) == 256
-    return np.array(p, np.int32)
+    return torch.from_numpy(hv).to(dev()), hv
 
 
 def _run(mb, a, b, pairs, mode, ratio, ori, stream):
-    tp = torch.from_numpy(np.ascontiguousarray(pairs, np.int32)).to(_dev())
+    tp = torch.from_numpy(np.ascontiguousarray(pairs, np.int32)).to(dev())
     out = mb.bow_pairs_device(a, b, tp, mode, ratio, ori, stream=stream.cuda_stream)
     stream.synchronize()
     return out.nmatches.cpu().numpy(), out.b2a.cpu().numpy(), out.a2b.cpu().numpy()
@@ -116,8 +86,8 @@ def _check_rows(n, b2a, a2b, want_n, want_b2a, na, where):
 
 
 def _oracle(bta, hfa, ia, hva, btb, hfb, ib, ratio, ori):
-    da, aa = bta.frame(ia)
-    db, ab = btb.frame(ib)
+    (ka, da), (kb, db) = bta.frame(ia), btb.frame(ib)
+    aa, ab = ka["angle"], kb["angle"]
     valid = np.ones(len(da), np.uint8) if hva is None else hva[ia, :len(da)]
     return po.search_by_bow(da, aa, valid, hfa[ia], db, ab, hfb[ib], ratio, ori), (da, aa, valid, db, ab)
 
@@ -132,7 +102,7 @@ def test_parity_per_pair_frame_mode(euroc, k, L):
     gv = vocs[k, L]
     mb = MatchBatch(0)
     tv, hv = _mask(bt, 11)
-    p256 = _pairs256()
+    p256 = pairs256()
     step = 0
     for levelsup in sorted({0, 2, 4, L}):
         fv, hfv = bt.transform(gv, (k, L, levelsup), levelsup)
@@ -219,8 +189,8 @@ def test_keyframe_mode_equals_the_model(euroc):
             n, b2a, a2b = _run(mb, bt.side(fv, va[0]), bt.side(fv, vb[0]), pairs, KEYFRAMES, ratio, ori, bt.s)
             nf, b2af, _ = _run(mb, bt.side(fv, va[0]), bt.side(fv, vb[0]), pairs, FRAME, ratio, ori, bt.s)
             for i, (ia, ib) in enumerate(pairs.tolist()):
-                da, aa = bt.frame(ia)
-                db, ab = bt.frame(ib)
+                (ka, da), (kb, db) = bt.frame(ia), bt.frame(ib)
+                aa, ab = ka["angle"], kb["angle"]
                 hva_i = None if va[1] is None else va[1][ia, :len(da)]
                 hvb_i = None if vb[1] is None else vb[1][ib, :len(db)]
                 wn, wb2a = mm.search_by_bow(da, aa, hva_i, hfv[ia], db, ab, hvb_i, hfv[ib], KEYFRAMES, ratio, ori)
@@ -238,7 +208,7 @@ def test_both_paths_give_the_same_bytes(euroc, monkeypatch):
     bt, vocs = euroc
     gv = vocs[10, 6]
     tv, _ = _mask(bt, 31)
-    pairs = _pairs256()[::8]
+    pairs = pairs256()[::8]
     default = MatchBatch(0)
     handles = {}
     for name, env in (("global", {"ORBX_MATCH_LDS": "0"}), ("trips", {"ORBX_MATCH_WAVE_NODE": "3"}), ("global trips", {"ORBX_MATCH_LDS": "0", "ORBX_MATCH_WAVE_NODE": "0"})):
@@ -281,10 +251,10 @@ def test_malformed_pairs(euroc):
         else:                                             # the neighbours are what they are without the malformed pairs
             assert n[i] == wn[i] > 0 and np.array_equal(b2a[i], wb2a[i]) and np.array_equal(a2b[i], wa2b[i]), i
     # either output alone
-    tp = torch.from_numpy(pairs).to(_dev())
+    tp = torch.from_numpy(pairs).to(dev())
     from orb_slam3_modified_amd.match import MatchResult
-    only_b = MatchResult(torch.zeros(len(pairs), dtype=torch.int32, device=_dev()), torch.zeros((len(pairs), bt.cap), dtype=torch.int32, device=_dev()), None)
-    only_a = MatchResult(torch.zeros(len(pairs), dtype=torch.int32, device=_dev()), None, torch.zeros((len(pairs), bt.cap), dtype=torch.int32, device=_dev()))
+    only_b = MatchResult(torch.zeros(len(pairs), dtype=torch.int32, device=dev()), torch.zeros((len(pairs), bt.cap), dtype=torch.int32, device=dev()), None)
+    only_a = MatchResult(torch.zeros(len(pairs), dtype=torch.int32, device=dev()), None, torch.zeros((len(pairs), bt.cap), dtype=torch.int32, device=dev()))
     mb.bow_pairs_device(side, side, tp, FRAME, 0.7, True, stream=bt.s.cuda_stream, out=only_b)
     mb.bow_pairs_device(side, side, tp, FRAME, 0.7, True, stream=bt.s.cuda_stream, out=only_a)
     bt.s.synchronize()
@@ -341,7 +311,7 @@ def test_two_calls_back_to_back_on_two_streams(euroc, monkeypatch):
     bt, vocs = euroc
     fv2, _ = bt.transform(vocs[10, 6], (10, 6, 2), 2)
     fv6, _ = bt.transform(vocs[10, 6], (10, 6, 6), 6)
-    p1, p2 = _pairs256(), _pairs256()[::-1].copy()
+    p1, p2 = pairs256(), pairs256()[::-1].copy()
     alone = MatchBatch(0)
     w1 = _run(alone, bt.side(fv6), bt.side(fv6), p1, FRAME, 0.7, True, bt.s)
     w2 = _run(alone, bt.side(fv2), bt.side(fv2), p2, KEYFRAMES, 0.9, False, bt.s)
@@ -349,8 +319,8 @@ def test_two_calls_back_to_back_on_two_streams(euroc, monkeypatch):
     monkeypatch.setenv("ORBX_MATCH_LDS", "0")             # the global-memory path: both calls use the handle's scratch
     mb = MatchBatch(0)
     monkeypatch.delenv("ORBX_MATCH_LDS")
-    s1, s2 = torch.cuda.Stream(device=_dev()), torch.cuda.Stream(device=_dev())
-    t1, t2 = torch.from_numpy(p1).to(_dev()), torch.from_numpy(p2).to(_dev())
+    s1, s2 = torch.cuda.Stream(device=dev()), torch.cuda.Stream(device=dev())
+    t1, t2 = torch.from_numpy(p1).to(dev()), torch.from_numpy(p2).to(dev())
     torch.cuda.synchronize()
     r1 = mb.bow_pairs_device(bt.side(fv6), bt.side(fv6), t1, FRAME, 0.7, True, stream=s1.cuda_stream)
     r2 = mb.bow_pairs_device(bt.side(fv2), bt.side(fv2), t2, KEYFRAMES, 0.9, False, stream=s2.cuda_stream)

@@ -58,10 +58,7 @@ def test_python_binding_covers_the_header():
         assert callable(getattr(initmatch.InitMatchBatch, m))
     assert initmatch.InitSide and initmatch.InitResult
     # the structure the binding passes is the header's: the same fields, in order and size
-    hdr = open(os.path.join(ROOT, "include", HEADER)).read()
-    body = hdr[hdr.index("typedef struct orbx_initmatch_side {"):hdr.index("} orbx_initmatch_side;")]
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    in_header = [n for decl in re.findall(r"([^;{]+);", body) for n in re.findall(r"\b(\w+)\s*(?:,|$)", decl.strip())]
+    in_header = abi_util.struct_fields(HEADER, "orbx_initmatch_side")
     assert in_header == [f for f, _ in _lib.OrbxInitMatchSide._fields_], in_header
     assert C.sizeof(_lib.OrbxInitMatchSide) == 3 * 8 + 2 * 4
     # the sizing formula the binding states is the library's: EuRoC's capacity fits the LDS, the initialisation extractor's does not

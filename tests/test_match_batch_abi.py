@@ -52,11 +52,7 @@ def test_python_binding_covers_the_header():
     for m in ("bow_pairs", "bow_pairs_device"):
         assert callable(getattr(match.MatchBatch, m))
     # the structure the binding passes is the header's
-    hdr = open(os.path.join(ROOT, "include", "orbx_match.h")).read()
-    body = hdr[hdr.index("typedef struct orbx_match_side {"):hdr.index("} orbx_match_side;")]
-    import re
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    in_header = [n for decl in re.findall(r"([^;{]+);", body) for n in re.findall(r"\b(\w+)\s*(?:,|$)", decl.strip())]
+    in_header = abi_util.struct_fields("orbx_match.h", "orbx_match_side")
     assert in_header == [f for f, _ in _lib.OrbxMatchSide._fields_], in_header
     assert C.sizeof(_lib.OrbxMatchSide) == 8 * 8 + 2 * 4
 

@@ -14,7 +14,6 @@ from __future__ import annotations
 
 import argparse
 import ctypes as C
-import json
 import os
 import subprocess
 import sys
@@ -24,12 +23,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from times_util import stats, timed, write_result  # noqa: E402
 OUT = os.path.join(ROOT, "profiles", "bow_batch_times_r8.txt")
-
-
-def stats(v):
-    v = np.asarray(v, np.float64)
-    return {"median": round(float(np.median(v)), 4), "min": round(float(v.min()), 4), "max": round(float(v.max()), 4), "n": int(len(v))}
 
 
 def clocks():
@@ -87,23 +82,11 @@ def run(B, repeats, train_frames):
     def leg_a3():
         bb.transform_device(desc, counts, B, cap, out=out, stream=s.cuda_stream, bow=False)
 
-    def timed(fn, n):
-        ts = []
-        for i in range(n + 3):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(s)
-            fn()
-            e1.record(s)
-            e1.synchronize()
-            if i >= 3:
-                ts.append(e0.elapsed_time(e1))
-        return stats(ts)
-
     torch.cuda.synchronize()
-    res["x_extract_batch_device_ms"] = timed(leg_x, repeats)
+    res["x_extract_batch_device_ms"] = timed(s, leg_x, repeats)
     for name, fn in (("a_transform_batch_device_ms", leg_a), ("a1_descent_all_rows_ms", leg_a1), ("a2_descent_and_bowvectors_ms", leg_a2),
                      ("a3_descent_and_featurevectors_ms", leg_a3)):
-        res[name] = timed(fn, repeats)
+        res[name] = timed(s, fn, repeats)
     torch.cuda.synchronize()
     hd, hc = desc.cpu().numpy(), counts.cpu().numpy()
     res["features_per_frame_median"] = int(np.median(hc[:, 0]))
@@ -129,9 +112,9 @@ def run(B, repeats, train_frames):
     db_ids, db_vals, db_n = out.bow_ids.repeat(rep, 1), out.bow_vals.repeat(rep, 1), out.bow_n.repeat(rep)
     ndb = db_n.shape[0]
     sc1, sc2 = z(B, B, dt=torch.float64), z(B, ndb, dt=torch.float64)
-    res["c_score_matrix_BxB_ms"] = timed(lambda: bb.score_matrix_device(out.bow_ids, out.bow_vals, out.bow_n, B, cap, out.bow_ids, out.bow_vals,
+    res["c_score_matrix_BxB_ms"] = timed(s, lambda: bb.score_matrix_device(out.bow_ids, out.bow_vals, out.bow_n, B, cap, out.bow_ids, out.bow_vals,
                                                                          out.bow_n, B, cap, scores=sc1, stream=s.cuda_stream), repeats)
-    res["c_score_matrix_Bx%d_ms" % ndb] = timed(lambda: bb.score_matrix_device(out.bow_ids, out.bow_vals, out.bow_n, B, cap, db_ids, db_vals, db_n,
+    res["c_score_matrix_Bx%d_ms" % ndb] = timed(s, lambda: bb.score_matrix_device(out.bow_ids, out.bow_vals, out.bow_n, B, cap, db_ids, db_vals, db_n,
                                                                                ndb, cap, scores=sc2, stream=s.cuda_stream), repeats)
     torch.cuda.synchronize()
     vecs = [r[0] for r in out.frames()]
@@ -163,12 +146,7 @@ def main():
     out = {"stamp": build.stamp(), "repeats": args.repeats, "clocks_before": clocks()}
     out["euroc_752x480"] = run(args.frames, args.repeats, args.train_frames)
     out["clocks_after"] = clocks()
-    print(json.dumps(out), flush=True)
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as fh:
-        fh.write("# tools/bow_batch_times.py: batched bag of words, HIP-event medians [min, max] of --repeats runs (ms); (b), (d): wall clock\n")
-        fh.write(json.dumps(out, indent=1) + "\n")
-    print("wrote", args.out)
+    write_result(args.out, "tools/bow_batch_times.py: batched bag of words, HIP-event medians [min, max] of --repeats runs (ms); (b), (d): wall clock", out)
 
 
 if __name__ == "__main__":

@@ -17,7 +17,6 @@ from __future__ import annotations
 
 import argparse
 import ctypes as C
-import json
 import os
 import subprocess
 import sys
@@ -27,12 +26,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from times_util import Extracted, pair_lists, stats, timed, write_result  # noqa: E402
 OUT = os.path.join(ROOT, "profiles", "initmatch_times_r10.txt")
-
-
-def stats(v):
-    v = np.asarray(v, np.float64)
-    return {"median": round(float(np.median(v)), 4), "min": round(float(v.min()), 4), "max": round(float(v.max()), 4), "n": int(len(v))}
 
 
 def no_chain_library():
@@ -50,38 +45,17 @@ def no_chain_library():
 
 def run(shape, params, B, lists, repeats, oracle, split):
     import torch
-    from orb_slam3_modified_amd import ORBextractor, _lib, synth
-    from orb_slam3_modified_amd._lib import KP_DTYPE, ptr
+    from orb_slam3_modified_amd import ORBextractor, _lib
+    from orb_slam3_modified_amd._lib import ptr
     from orb_slam3_modified_amd.initmatch import LDS_MAX, InitMatchBatch, InitSide, lds_bytes
     H, W = shape
     window, ratio, bounds = 100, 0.9, (0.0, 0.0, float(W), float(H))
     ex = ORBextractor(*params, device_id=0)
     cap = ex.capacity
-    dev = torch.device("cuda:0")
-    s = torch.cuda.Stream(device=dev)
-    t = torch.from_numpy(synth.make_stream(B, H, W)).to(dev)
-    z = lambda *sh, dt=torch.uint8: torch.zeros(sh, dtype=dt, device=dev)   # noqa: E731
-    kps, desc, counts = z(B, cap, 28), z(B, cap, 32), z(B, 2, dt=torch.int32)
-    p = lambda x: x.data_ptr()   # noqa: E731
+    x = Extracted(ex, B, H, W, repeats)
+    s, dev, kps, desc, counts, hk, hd, hc = x.s, x.dev, x.kps, x.desc, x.counts, x.hk, x.hd, x.hc
     res = {"frames": B, "capacity": cap, "window": window, "nn_ratio": ratio, "path": "lds" if lds_bytes(cap, cap) <= LDS_MAX else "global"}
-
-    def timed(fn, n):
-        ts = []
-        for i in range(n + 3):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(s)
-            fn()
-            e1.record(s)
-            e1.synchronize()
-            if i >= 3:
-                ts.append(e0.elapsed_time(e1))
-        return stats(ts)
-
-    torch.cuda.synchronize()
-    res["d_extract_batch_device_ms"] = timed(lambda: ex.extract_batch_device(p(t), B, H, W, W, H * W, p(kps), p(desc), p(counts), (0, 1000),
-                                                                             stream=s.cuda_stream), repeats)
-    hk = kps.cpu().numpy().view(KP_DTYPE).reshape(B, cap)
-    hd, hc = desc.cpu().numpy(), counts.cpu().numpy()
+    res["d_extract_batch_device_ms"] = x.extract_ms
     host = [(np.ascontiguousarray(hk[f, :hc[f, 0]]), np.ascontiguousarray(hd[f, :hc[f, 0]])) for f in range(B)]
     res["keypoints_per_frame_median"] = int(np.median(hc[:, 0]))
     res["level0_per_frame_median"] = int(np.median([(k["octave"] == 0).sum() for k, _ in host]))
@@ -94,14 +68,14 @@ def run(shape, params, B, lists, repeats, oracle, split):
         torch.cuda.synchronize()
         out = mb.pairs_device(side, side, tp, bounds, window, ratio, True, stream=s.cuda_stream)
         r = res.setdefault(name, {})
-        r["a_batched_device_call_ms"] = timed(lambda: mb.pairs_device(side, side, tp, bounds, window, ratio, True, stream=s.cuda_stream, out=out), repeats)
+        r["a_batched_device_call_ms"] = timed(s, lambda: mb.pairs_device(side, side, tp, bounds, window, ratio, True, stream=s.cuda_stream, out=out), repeats)
         r["a_over_d"] = round(r["a_batched_device_call_ms"]["median"] / res["d_extract_batch_device_ms"]["median"], 4)
         torch.cuda.synchronize()
         gn, g12 = out.nmatches.cpu().numpy(), out.matches12.cpu().numpy()
         r["matches_per_pair_median"] = int(np.median(gn))
         if nc is not None:
             o2 = nc.pairs_device(side, side, tp, bounds, window, ratio, True, stream=s.cuda_stream)
-            r["split_without_phase_b_ms"] = timed(lambda: nc.pairs_device(side, side, tp, bounds, window, ratio, True, stream=s.cuda_stream, out=o2), repeats)
+            r["split_without_phase_b_ms"] = timed(s, lambda: nc.pairs_device(side, side, tp, bounds, window, ratio, True, stream=s.cuda_stream, out=o2), repeats)
             r["split_chain_share_of_a"] = round(1.0 - r["split_without_phase_b_ms"]["median"] / r["a_batched_device_call_ms"]["median"], 3)
         # (b) the per-pair loop of before
         m12, n_ = np.zeros(cap, np.int32), C.c_int(0)
@@ -143,17 +117,10 @@ def main():
     from orb_slam3_modified_amd import build
     B = args.frames
     out = {"stamp": build.stamp(), "repeats": args.repeats}
-    lists = {"256_pairs_f_f1": np.array([(f, (f + 1) % B) for f in range(B)], np.int32),
-             "2560_pairs_f_ten_others": np.array([(f, (f + j) % B) for f in range(B) for j in range(1, 11)], np.int32)}
-    out["euroc_752x480_1000"] = run((480, 752), (1000, 1.2, 8, 20, 7), B, lists, args.repeats, not args.no_oracle, not args.no_split)
+    out["euroc_752x480_1000"] = run((480, 752), (1000, 1.2, 8, 20, 7), B, pair_lists(B), args.repeats, not args.no_oracle, not args.no_split)
     out["vga_640x480_5000"] = run((480, 640), (5000, 1.2, 8, 20, 7), 33, {"32_pairs_f_f1": np.array([(f, f + 1) for f in range(32)], np.int32)},
                                   args.repeats, not args.no_oracle, not args.no_split)
-    print(json.dumps(out), flush=True)
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as fh:
-        fh.write("# tools/initmatch_times.py: batched SearchForInitialization, HIP-event medians [min, max] of --repeats runs (ms); (b), (c): wall clock\n")
-        fh.write(json.dumps(out, indent=1) + "\n")
-    print("wrote", args.out)
+    write_result(args.out, "tools/initmatch_times.py: batched SearchForInitialization, HIP-event medians [min, max] of --repeats runs (ms); (b), (c): wall clock", out)
 
 
 if __name__ == "__main__":

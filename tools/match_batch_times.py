@@ -14,7 +14,6 @@ from __future__ import annotations
 
 import argparse
 import ctypes as C
-import json
 import os
 import sys
 import time
@@ -23,12 +22,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from times_util import Extracted, pair_lists, stats, timed, write_result  # noqa: E402
 OUT = os.path.join(ROOT, "profiles", "match_batch_times_r9.txt")
-
-
-def stats(v):
-    v = np.asarray(v, np.float64)
-    return {"median": round(float(np.median(v)), 4), "min": round(float(v.min()), 4), "max": round(float(v.max()), 4), "n": int(len(v))}
 
 
 def csr(fv):
@@ -43,18 +38,12 @@ def csr(fv):
 def run(B, repeats, train_frames, oracle):
     import torch
     from orb_slam3_modified_amd import ORBextractor, ORBVocabulary, _lib, synth
-    from orb_slam3_modified_amd._lib import KP_DTYPE, ptr
+    from orb_slam3_modified_amd._lib import ptr
     from orb_slam3_modified_amd.bow import BowBatch
     from orb_slam3_modified_amd.match import FRAME, MatchBatch, MatchSide
     H, W, params, ratio = 480, 752, (1000, 1.2, 8, 20, 7), 0.7
     ex = ORBextractor(*params, device_id=0)
     cap = ex.capacity
-    dev = torch.device("cuda:0")
-    s = torch.cuda.Stream(device=dev)
-    t = torch.from_numpy(synth.make_stream(B, H, W)).to(dev)
-    z = lambda *shape, dt=torch.uint8: torch.zeros(shape, dtype=dt, device=dev)   # noqa: E731
-    kps, desc, counts = z(B, cap, 28), z(B, cap, 32), z(B, 2, dt=torch.int32)
-    p = lambda x: x.data_ptr()   # noqa: E731
     trainer, docs = ex.clone(), []
     for a in range(0, train_frames, 64):
         docs += [r[2] for r in trainer.extract_batch(synth.make_stream(64, 480, 640, 9000 + a), (0, 1000))]
@@ -63,31 +52,15 @@ def run(B, repeats, train_frames, oracle):
     res = {"frames": B, "capacity": cap, "nn_ratio": ratio, "training_descriptors": int(sum(len(d) for d in docs)), "tree": gv.info()}
     L = _lib.lib()
     mb = MatchBatch(0)
-
-    def timed(fn, n):
-        ts = []
-        for i in range(n + 3):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(s)
-            fn()
-            e1.record(s)
-            e1.synchronize()
-            if i >= 3:
-                ts.append(e0.elapsed_time(e1))
-        return stats(ts)
-
-    torch.cuda.synchronize()
-    res["d_extract_batch_device_ms"] = timed(lambda: ex.extract_batch_device(p(t), B, H, W, W, H * W, p(kps), p(desc), p(counts), (0, 1000),
-                                                                             stream=s.cuda_stream), repeats)
-    hk = kps.cpu().numpy().view(KP_DTYPE).reshape(B, cap)
-    hd, hc = desc.cpu().numpy(), counts.cpu().numpy()
-    lists = {"256_pairs_f_f1": np.array([(f, (f + 1) % B) for f in range(B)], np.int32),
-             "2560_pairs_f_ten_others": np.array([(f, (f + j) % B) for f in range(B) for j in range(1, 11)], np.int32)}
+    x = Extracted(ex, B, H, W, repeats)
+    res["d_extract_batch_device_ms"] = x.extract_ms
+    s, dev, kps, desc, counts, hk, hd, hc = x.s, x.dev, x.kps, x.desc, x.counts, x.hk, x.hd, x.hc
+    lists = pair_lists(B)
     for levelsup, names in ((4, list(lists)), (6, ["256_pairs_f_f1"])):
         bb = BowBatch(gv, levelsup)
         fv = bb.transform_device(desc, counts, B, cap, stream=s.cuda_stream, bow=False)
         leg = res.setdefault(f"levelsup_{levelsup}", {})
-        leg["d_transform_featurevectors_ms"] = timed(lambda: bb.transform_device(desc, counts, B, cap, out=fv, stream=s.cuda_stream, bow=False), repeats)
+        leg["d_transform_featurevectors_ms"] = timed(s, lambda: bb.transform_device(desc, counts, B, cap, out=fv, stream=s.cuda_stream, bow=False), repeats)
         side = MatchSide.of(kps, desc, counts, fv, B, cap)
         fn, fp, ff, fc = (fv.fv_node.cpu().numpy().view(np.uint32), fv.fv_ptr.cpu().numpy(), fv.fv_feat.cpu().numpy().view(np.uint32), fv.fv_n.cpu().numpy())
         hfv = [{int(fn[f, j]): ff[f, fp[f, j]:fp[f, j + 1]].astype(np.int64).tolist() for j in range(int(fc[f]))} for f in range(B)]
@@ -101,7 +74,7 @@ def run(B, repeats, train_frames, oracle):
             tp = torch.from_numpy(pairs).to(dev)
             out = mb.bow_pairs_device(side, side, tp, FRAME, ratio, True, stream=s.cuda_stream)
             r = leg.setdefault(name, {})
-            r["a_batched_device_call_ms"] = timed(lambda: mb.bow_pairs_device(side, side, tp, FRAME, ratio, True, stream=s.cuda_stream, out=out), repeats)
+            r["a_batched_device_call_ms"] = timed(s, lambda: mb.bow_pairs_device(side, side, tp, FRAME, ratio, True, stream=s.cuda_stream, out=out), repeats)
             torch.cuda.synchronize()
             gn, gb2a = out.nmatches.cpu().numpy(), out.b2a.cpu().numpy()
             r["matches_per_pair_median"] = int(np.median(gn))
@@ -143,12 +116,7 @@ def main():
     from orb_slam3_modified_amd import build
     out = {"stamp": build.stamp(), "repeats": args.repeats}
     out["euroc_752x480"] = run(args.frames, args.repeats, args.train_frames, not args.no_oracle)
-    print(json.dumps(out), flush=True)
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as fh:
-        fh.write("# tools/match_batch_times.py: batched SearchByBoW, HIP-event medians [min, max] of --repeats runs (ms); (b), (c): wall clock\n")
-        fh.write(json.dumps(out, indent=1) + "\n")
-    print("wrote", args.out)
+    write_result(args.out, "tools/match_batch_times.py: batched SearchByBoW, HIP-event medians [min, max] of --repeats runs (ms); (b), (c): wall clock", out)
 
 
 if __name__ == "__main__":

@@ -22,16 +22,12 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from times_util import stats  # noqa: E402
 OUT = os.path.join(ROOT, "profiles", "stereo_batch_times_r7.txt")
 CONFIGS = {
     "euroc_752x480": dict(shape=(480, 752), params=(1200, 1.2, 8, 20, 7), mb=0.11, mbf=47.90639384423901),
     "kitti_1241x376": dict(shape=(376, 1241), params=(2000, 1.2, 8, 20, 7), mb=0.53716, mbf=0.53716 * 718.856),
 }
-
-
-def stats(v):
-    v = np.asarray(v, np.float64)
-    return {"median": round(float(np.median(v)), 4), "min": round(float(v.min()), 4), "max": round(float(v.max()), 4), "n": int(len(v))}
 
 
 def run(name, cfg, B, repeats, device_only=False):
