@@ -18,6 +18,7 @@ STEREO_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_stereo.so")  
 BOW_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_bow.so")         # the batched bag of words (include/orbx_bow.h)
 MATCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_match.so")     # the batched SearchByBoW (include/orbx_match.h)
 INITMATCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_initmatch.so")   # the batched SearchForInitialization (include/orbx_initmatch.h)
+TRIMATCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_trimatch.so")     # the batched SearchForTriangulation (include/orbx_trimatch.h)
 
 ORBX_OK, ORBX_E_INVALID, ORBX_E_EMPTY, ORBX_E_DEVICE, ORBX_E_CAPACITY, ORBX_E_FORMAT = 0, -1, -2, -3, -4, -5
 NUM_KERNELS = 6
@@ -304,9 +305,31 @@ def initmatch_lib(path: str = INITMATCH_LIB_PATH) -> C.CDLL:
     return M
 
 
+class OrbxTriMatchSide(C.Structure):
+    """orbx_trimatch_side (include/orbx_trimatch.h)."""
+    _fields_ = [("d_kps", C.c_void_p), ("d_desc", C.c_void_p), ("d_counts", C.c_void_p), ("d_fv_node", C.c_void_p), ("d_fv_ptr", C.c_void_p),
+                ("d_fv_feat", C.c_void_p), ("d_fv_n", C.c_void_p), ("d_has_point", C.c_void_p), ("d_uright", C.c_void_p), ("nframes", C.c_int),
+                ("capacity", C.c_int)]
+
+
+def trimatch_lib() -> C.CDLL:
+    """liborbx_trimatch.so.  `_orbx_trimatch_symbols`: every name of include/orbx_trimatch.h, bound here with its signature."""
+    vp, i32, sp, fp = C.c_void_p, C.c_int, C.POINTER(OrbxTriMatchSide), C.POINTER(C.c_float)
+    sig = {
+        "orbx_trimatch_create": (i32, [C.POINTER(vp), i32]),
+        "orbx_trimatch_destroy": (None, [vp]),
+        "orbx_trimatch_last_error": (C.c_char_p, [vp]),
+        "orbx_trimatch_pairs_device": (i32, [vp, sp, sp, vp, i32, vp, fp, fp, i32, i32, i32, i32, vp, vp, vp]),
+        "orbx_trimatch_pairs": (i32, [vp, sp, sp, vp, i32, vp, fp, fp, i32, i32, i32, i32, vp, vp]),
+    }
+    M = _load_side(TRIMATCH_LIB_PATH, sig)
+    M._orbx_trimatch_symbols = tuple(sig)
+    return M
+
+
 class SideHandle:
     """A handle of a side library whose entry points are <prefix>_create / _destroy / _last_error (StereoBatch, BowBatch, MatchBatch,
-    InitMatchBatch)."""
+    InitMatchBatch, TriMatchBatch)."""
 
     def __init__(self, library: C.CDLL, prefix: str, *create_args):
         self._L, self._prefix, self._h = library, prefix, C.c_void_p(0)
