@@ -19,6 +19,7 @@ BOW_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_bow.so")        
 MATCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_match.so")     # the batched SearchByBoW (include/orbx_match.h)
 INITMATCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_initmatch.so")   # the batched SearchForInitialization (include/orbx_initmatch.h)
 TRIMATCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_trimatch.so")     # the batched SearchForTriangulation (include/orbx_trimatch.h)
+FUSE_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_fuse.so")             # the batched Fuse search (include/orbx_fuse.h)
 
 ORBX_OK, ORBX_E_INVALID, ORBX_E_EMPTY, ORBX_E_DEVICE, ORBX_E_CAPACITY, ORBX_E_FORMAT = 0, -1, -2, -3, -4, -5
 NUM_KERNELS = 6
@@ -327,9 +328,31 @@ def trimatch_lib() -> C.CDLL:
     return M
 
 
+class OrbxFuseSide(C.Structure):
+    """orbx_fuse_side (include/orbx_fuse.h)."""
+    _fields_ = [("d_kps", C.c_void_p), ("d_desc", C.c_void_p), ("d_counts", C.c_void_p), ("d_uright", C.c_void_p), ("d_gridparm", C.c_void_p),
+                ("nframes", C.c_int), ("capacity", C.c_int)]
+
+
+def fuse_lib() -> C.CDLL:
+    """liborbx_fuse.so.  `_orbx_fuse_symbols`: every name of include/orbx_fuse.h, bound here with its signature."""
+    vp, i32, sp, fp = C.c_void_p, C.c_int, C.POINTER(OrbxFuseSide), C.POINTER(C.c_float)
+    sig = {
+        "orbx_fuse_create": (i32, [C.POINTER(vp), i32]),
+        "orbx_fuse_destroy": (None, [vp]),
+        "orbx_fuse_last_error": (C.c_char_p, [vp]),
+        "orbx_fuse_grids_device": (i32, [vp, sp, vp]),
+        "orbx_fuse_search_device": (i32, [vp, sp, vp, vp, i32, vp, i32, vp, i32, fp, i32, i32, i32, vp, vp, vp, vp]),
+        "orbx_fuse_search": (i32, [vp, sp, vp, vp, i32, vp, i32, vp, i32, fp, i32, i32, i32, vp, vp, vp]),
+    }
+    M = _load_side(FUSE_LIB_PATH, sig)
+    M._orbx_fuse_symbols = tuple(sig)
+    return M
+
+
 class SideHandle:
     """A handle of a side library whose entry points are <prefix>_create / _destroy / _last_error (StereoBatch, BowBatch, MatchBatch,
-    InitMatchBatch, TriMatchBatch)."""
+    InitMatchBatch, TriMatchBatch, FuseBatch)."""
 
     def __init__(self, library: C.CDLL, prefix: str, *create_args):
         self._L, self._prefix, self._h = library, prefix, C.c_void_p(0)
