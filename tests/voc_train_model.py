@@ -51,9 +51,21 @@ class NoConvergence(RuntimeError):
     pass
 
 
+def _popcount64(v: np.ndarray) -> np.ndarray:
+    if hasattr(np, "bitwise_count"):
+        return np.bitwise_count(v)
+    return _POP[v.view(np.uint8).reshape(v.shape + (8,))].sum(-1)
+
+
 def _dist(x: np.ndarray, c: np.ndarray) -> np.ndarray:
-    """FORB::distance of every row of x (n, 32) to every centre c (m, 32): (n, m) int."""
-    return _POP[x[:, None, :] ^ c[None, :, :]].sum(-1)
+    """FORB::distance of every row of x (n, 32) to every centre c (m, 32): (n, m) int.  A bit count over four uint64 words per pair (the
+    (n, m, 32) byte-table lookup takes minutes on 10^5 rows)."""
+    xw = np.ascontiguousarray(x, np.uint8).reshape(-1, 32).view(np.uint64)
+    cw = np.ascontiguousarray(c, np.uint8).reshape(-1, 32).view(np.uint64)
+    out = np.zeros((len(xw), len(cw)), np.int64)
+    for j in range(len(cw)):
+        out[:, j] = _popcount64(xw ^ cw[j]).sum(1)
+    return out
 
 
 def _mean(x: np.ndarray) -> np.ndarray:
@@ -63,17 +75,20 @@ def _mean(x: np.ndarray) -> np.ndarray:
     return np.packbits(cnt >= n // 2 + n % 2)
 
 
-def create(desc: np.ndarray, offsets, k: int, L: int, weighting: int, seed: int, max_iterations: int = 10000):
-    """-> (parent, is_leaf, desc, weight) over all nodes, root (id 0) included, and {'empty_clusters', 'iterations'}."""
+def create(desc: np.ndarray, offsets, k: int, L: int, weighting: int, seed: int, max_iterations: int = 10000, trace: list | None = None):
+    """-> (parent, is_leaf, desc, weight) over all nodes, root (id 0) included, and {'empty_clusters', 'iterations'}.
+    `trace`, when given, receives one dict per k-means node in the reference's depth-first order: level, n, first (the first centre's index),
+    draws (one (n, sum, ceil(cut), chosen index) per k-means++ draw) and kc (the centres seeded)."""
     X = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
     offsets = np.asarray(offsets, np.int64)
     rng = GlibcRand(seed)
     parent, ndesc = [0], [np.zeros(32, np.uint8)]
     stats = {"empty_clusters": 0, "iterations": 0}
 
-    def kmeans(x):
+    def kmeans(x, level):
         n = len(x)
         i0 = rng.random_int(0, n - 1)
+        draws = []
         cents = [x[i0]]
         md = _dist(x, x[i0][None])[:, 0].astype(np.int64)
         while len(cents) < k:
@@ -84,8 +99,11 @@ def create(desc: np.ndarray, offsets, k: int, L: int, weighting: int, seed: int,
             while cut == 0.0:
                 cut = rng.random_value(0.0, float(s))
             idx = int(np.searchsorted(np.cumsum(md), math.ceil(cut), side="left"))
+            draws.append((n, s, math.ceil(cut), min(idx, n - 1)))
             cents.append(x[min(idx, n - 1)])
             md = np.minimum(md, _dist(x, x[min(idx, n - 1)][None])[:, 0])
+        if trace is not None:
+            trace.append({"level": level, "n": n, "first": i0, "draws": draws, "kc": len(cents)})
         c = np.array(cents, np.uint8)
         assoc = np.argmin(_dist(x, c), axis=1)   # argmin returns the first minimum: the strict < of the reference
         it = 1
@@ -112,7 +130,7 @@ def create(desc: np.ndarray, offsets, k: int, L: int, weighting: int, seed: int,
         if len(x) <= k:
             c, assoc = x.copy(), np.arange(len(x))
         else:
-            c, assoc = kmeans(x)
+            c, assoc = kmeans(x, level)
         first = len(parent)
         for j in range(len(c)):
             parent.append(pid)
@@ -151,12 +169,12 @@ def descend(parent, leaf, D, X):
     children = [[] for _ in range(len(parent))]
     for i in range(1, len(parent)):
         children[parent[i]].append(i)
-    out = np.zeros(len(X), np.int64)
-    for r in range(len(X)):
-        nid = 0
-        while not leaf[nid] or nid == 0:
-            ch = children[nid]
-            d = _POP[D[ch] ^ X[r]].sum(1)
-            nid = ch[int(np.argmin(d))]
-        out[r] = nid
+    out = np.zeros(len(X), np.int64)   # every row starts at the root; a child's id is above its parent's, so one pass in id order descends all
+    for nid in range(len(parent)):
+        ch = children[nid]
+        if not ch:
+            continue
+        rows = np.nonzero(out == nid)[0]
+        if len(rows):
+            out[rows] = np.array(ch, np.int64)[np.argmin(_dist(X[rows], D[ch]), axis=1)]
     return out

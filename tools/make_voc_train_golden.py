@@ -7,8 +7,11 @@ arrays exactly (parent, leaf flag, descriptor, weight as float64).  Needs the re
 only where that is present.  Configurations the reference does not complete (it dereferences a released cv::Mat on an empty cluster) are
 reported and left out.
 
-  python tools/make_voc_train_golden.py [--check]
+  python tools/make_voc_train_golden.py [--large] [--check]
     --check  rebuild in memory and compare with the committed file (exit 1 on a difference)
+    --large  the second file, tests/golden/voc_train_large.npz: the reference's create on the generated sets of tests/voc_train_cases.py
+             (outputs, settings and the inputs' SHA-256 only; the numpy model's empty_clusters / iterations and its device / host node
+             counts per threshold go under model_ keys, the reference does not report them)
 time_reference() times the reference-compiled create on other descriptors (tools/voc_train_times.py uses it).
 """
 from __future__ import annotations
@@ -28,6 +31,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 REFROOT = os.environ.get("REFROOT", "/root/reference")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "voc_train.npz")
+GOLDEN_LARGE = os.path.join(ROOT, "tests", "golden", "voc_train_large.npz")
 DBOW = ["DBoW2/BowVector.cpp", "DBoW2/FeatureVector.cpp", "DBoW2/ScoringObject.cpp", "DBoW2/FORB.cpp", "DUtils/Random.cpp", "DUtils/Timestamp.cpp"]
 
 # (name, descriptor set, k, L, weighting, scoring, seed); weighting 0 TF_IDF, 1 TF, 2 IDF, 3 BINARY
@@ -133,6 +137,36 @@ def make() -> dict:
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+def make_large() -> dict:
+    """Every case of tests/voc_train_cases.py through the reference; a case it does not complete is an error (take another seed)."""
+    from tests import voc_train_cases as VC, voc_train_model as M
+    tmp = tempfile.mkdtemp(prefix="voc_train_ref_")
+    try:
+        exe = build_driver(tmp)
+        out = {"cases": np.array(list(VC.CASES))}
+        for name, c in VC.CASES.items():
+            desc, off = VC.generate(name)
+            res, info = run_reference(exe, tmp, desc, off, c["k"], c["L"], c["weighting"], c["scoring"], c["seed"])
+            if res is None:
+                raise SystemExit(f"reference create did not complete on {name} (exit {info}): take another seed")
+            trace = []
+            _, st = M.create(desc, off, c["k"], c["L"], c["weighting"], c["seed"], trace=trace)
+            out[f"cfg_{name}"] = np.array([c["k"], c["L"], c["weighting"], c["scoring"], c["seed"], c["mid"]], np.int64)
+            out[f"gen_{name}"] = np.array(c["gen"])
+            out[f"args_{name}"] = np.array(c["args"], np.float64)
+            out[f"off_{name}"] = off
+            out[f"sha_{name}"] = np.array(VC.digest(desc, off))
+            for key, a in zip(("parent", "leaf", "desc", "weight"), res):
+                out[f"out_{name}_{key}"] = a
+            out[f"model_{name}_stats"] = np.array([st["empty_clusters"], st["iterations"]], np.int64)
+            out[f"model_{name}_split"] = np.array([(thr,) + VC.split(trace, c["k"], thr)
+                                                   for thr in (c["k"] + 1, c["mid"], VC.DEFAULT_MIN_NODE, VC.HOST_ONLY)], np.int64)
+            print(f"{name}: {len(desc)} descriptors, {len(res[0])} nodes, reference {info:.1f} s", file=sys.stderr)
+        return out
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
 def time_reference(desc, off, k, L, w=0, s=0, seed=1):
     """(wall seconds, node arrays) of the reference-compiled create (one core) on the given descriptors."""
     tmp = tempfile.mkdtemp(prefix="voc_train_ref_")
@@ -159,18 +193,20 @@ def cpu_name() -> str:
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--check", action="store_true")
+    ap.add_argument("--large", action="store_true")
     a = ap.parse_args()
-    out = make()
+    out = make_large() if a.large else make()
+    golden, pin = (GOLDEN_LARGE, "LARGE_SHA256") if a.large else (GOLDEN, "GOLDEN_SHA256")
     if a.check:
-        z = np.load(GOLDEN)
+        z = np.load(golden)
         same = sorted(z.files) == sorted(out) and all(np.array_equal(z[f], out[f]) for f in z.files)
         print("golden reproduced bit for bit" if same else "golden DIFFERS")
         sys.exit(0 if same else 1)
-    np.savez_compressed(GOLDEN, **out)
+    np.savez_compressed(golden, **out)
     import hashlib
-    sha = hashlib.sha256(open(GOLDEN, "rb").read()).hexdigest()
-    print(f"wrote {GOLDEN}: {len(out['configs'])} configurations, {os.path.getsize(GOLDEN)} bytes, sha256 {sha}"
-          " (tests/test_voc_train_model.py: GOLDEN_SHA256)")
+    sha = hashlib.sha256(open(golden, "rb").read()).hexdigest()
+    print(f"wrote {golden}: {len(out['cases' if a.large else 'configs'])} configurations, {os.path.getsize(golden)} bytes, sha256 {sha}"
+          f" (tests/test_voc_train_model.py: {pin})")
 
 
 if __name__ == "__main__":
