@@ -20,6 +20,7 @@ MATCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_match.so")    
 INITMATCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_initmatch.so")   # the batched SearchForInitialization (include/orbx_initmatch.h)
 TRIMATCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_trimatch.so")     # the batched SearchForTriangulation (include/orbx_trimatch.h)
 FUSE_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_fuse.so")             # the batched Fuse search (include/orbx_fuse.h)
+MPDESC_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_mpdesc.so")         # the batched ComputeDistinctiveDescriptors (include/orbx_mpdesc.h)
 
 ORBX_OK, ORBX_E_INVALID, ORBX_E_EMPTY, ORBX_E_DEVICE, ORBX_E_CAPACITY, ORBX_E_FORMAT = 0, -1, -2, -3, -4, -5
 NUM_KERNELS = 6
@@ -350,9 +351,29 @@ def fuse_lib() -> C.CDLL:
     return M
 
 
+class OrbxMpdescSide(C.Structure):
+    """orbx_mpdesc_side (include/orbx_mpdesc.h)."""
+    _fields_ = [("d_desc", C.c_void_p), ("d_counts", C.c_void_p), ("nframes", C.c_int), ("capacity", C.c_int)]
+
+
+def mpdesc_lib() -> C.CDLL:
+    """liborbx_mpdesc.so.  `_orbx_mpdesc_symbols`: every name of include/orbx_mpdesc.h, bound here with its signature."""
+    vp, i32, sp = C.c_void_p, C.c_int, C.POINTER(OrbxMpdescSide)
+    sig = {
+        "orbx_mpdesc_create": (i32, [C.POINTER(vp), i32]),
+        "orbx_mpdesc_destroy": (None, [vp]),
+        "orbx_mpdesc_last_error": (C.c_char_p, [vp]),
+        "orbx_mpdesc_select_device": (i32, [vp, sp, vp, i32, vp, i32, vp, vp, i32, vp, vp, vp]),
+        "orbx_mpdesc_select": (i32, [vp, sp, vp, i32, vp, i32, vp, vp, i32, vp, vp]),
+    }
+    M = _load_side(MPDESC_LIB_PATH, sig)
+    M._orbx_mpdesc_symbols = tuple(sig)
+    return M
+
+
 class SideHandle:
     """A handle of a side library whose entry points are <prefix>_create / _destroy / _last_error (StereoBatch, BowBatch, MatchBatch,
-    InitMatchBatch, TriMatchBatch, FuseBatch)."""
+    InitMatchBatch, TriMatchBatch, FuseBatch, DistinctBatch)."""
 
     def __init__(self, library: C.CDLL, prefix: str, *create_args):
         self._L, self._prefix, self._h = library, prefix, C.c_void_p(0)
