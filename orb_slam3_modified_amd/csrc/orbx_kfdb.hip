@@ -406,6 +406,7 @@ int orbx_kfdb_query(orbx_kfdb* db, const uint32_t* q_ids, const double* q_vals, 
   kfdb_list_order(db, common, first, order);
   int minc = (int)((float)maxc * 0.8f);
   if (minc < min_words_floor) minc = min_words_floor;
+  if (order.empty()) minc = 0;   // every Detect* routine returns before its thresholds when no keyframe shares a word (:136, :501, :637, :758)
   if ((int)order.size() > cap) return set_err(ctx, ORBX_E_CAPACITY, "orbx_kfdb_query: output capacity below the number of keyframes sharing a word");
   for (size_t i = 0; i < order.size(); i++) {
     const int r = order[i];
@@ -465,8 +466,8 @@ int orbx_kfdb_score(orbx_kfdb* db, const uint32_t* q_ids, const double* q_vals, 
     row[i] = it->second;
     sel[it->second] = 1;
   }
-  if (nq == 0) {   // L1Scoring::score of an empty vector against anything: no common term, -0.0 / 2 -> the reference returns -0 = 0
-    for (int i = 0; i < n; i++) scores[i] = 0.0;
+  if (nq == 0) {   // L1Scoring::score of an empty vector against anything: no common term, and -score / 2.0 of +0.0 is -0.0 (ScoringObject.cpp:65)
+    for (int i = 0; i < n; i++) scores[i] = -0.0;
     return ORBX_OK;
   }
   int rc = kfdb_begin(db, "orbx_kfdb_score", q_ids, q_vals, nq);
