@@ -26,6 +26,7 @@
 
 #include "orbx.h"
 #include "orbx_cv_compat.h"
+#include "orbx_score.h"
 #include "orbx_train.h"
 
 // ---- DBoW2::BowVector / DBoW2::FeatureVector ---------------------------------------------------------------------------------
@@ -288,6 +289,18 @@ class ORBVocabulary {
     for (const auto& kv : a) { ia.push_back(kv.first); va.push_back(kv.second); }
     for (const auto& kv : b) { ib.push_back(kv.first); vb.push_back(kv.second); }
     return orbx_bow_score_l1(ia.data(), va.data(), (int)ia.size(), ib.data(), vb.data(), (int)ib.size());
+  }
+
+  // scoreAs(a, b, scoring): TemplatedVocabulary::score as a vocabulary whose header line names `scoring` computes it (a DBoW2::ScoringType
+  // value, 0 .. 5; ScoringObject.cpp, all six functions; include/orbx_score.h).  score(a, b) above is L1Scoring::score whatever the loaded
+  // file's header says; a vocabulary trained or saved under another scoring is scored with this member.  The vectors must carry that
+  // scoring's norm, which transform gives them.  Only a program that calls scoreAs has to link liborbx_score.so.
+  double scoreAs(const DBoW2::BowVector& a, const DBoW2::BowVector& b, int scoring) const {
+    std::vector<uint32_t> ia, ib;
+    std::vector<double> va, vb;
+    for (const auto& kv : a) { ia.push_back(kv.first); va.push_back(kv.second); }
+    for (const auto& kv : b) { ib.push_back(kv.first); vb.push_back(kv.second); }
+    return orbx_score_pair(scoring, ia.data(), va.data(), (int)ia.size(), ib.data(), vb.data(), (int)ib.size());
   }
 
   orbx_voc* Handle() { return voc_; }

@@ -21,6 +21,7 @@ INITMATCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_initmatch.
 TRIMATCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_trimatch.so")     # the batched SearchForTriangulation (include/orbx_trimatch.h)
 FUSE_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_fuse.so")             # the batched Fuse search (include/orbx_fuse.h)
 MPDESC_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_mpdesc.so")         # the batched ComputeDistinctiveDescriptors (include/orbx_mpdesc.h)
+SCORE_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_score.so")           # the six DBoW2 scorings (include/orbx_score.h)
 
 ORBX_OK, ORBX_E_INVALID, ORBX_E_EMPTY, ORBX_E_DEVICE, ORBX_E_CAPACITY, ORBX_E_FORMAT = 0, -1, -2, -3, -4, -5
 NUM_KERNELS = 6
@@ -371,9 +372,25 @@ def mpdesc_lib() -> C.CDLL:
     return M
 
 
+def score_lib() -> C.CDLL:
+    """liborbx_score.so.  `_orbx_score_symbols`: every name of include/orbx_score.h, bound here with its signature."""
+    vp, i32 = C.c_void_p, C.c_int
+    sig = {
+        "orbx_score_create": (i32, [C.POINTER(vp), i32]),
+        "orbx_score_destroy": (None, [vp]),
+        "orbx_score_last_error": (C.c_char_p, [vp]),
+        "orbx_score_pair": (C.c_double, [i32, vp, vp, i32, vp, vp, i32]),
+        "orbx_score_matrix_device": (i32, [vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, i32, i32, vp, vp]),
+        "orbx_score_matrix": (i32, [vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp]),
+    }
+    M = _load_side(SCORE_LIB_PATH, sig)
+    M._orbx_score_symbols = tuple(sig)
+    return M
+
+
 class SideHandle:
     """A handle of a side library whose entry points are <prefix>_create / _destroy / _last_error (StereoBatch, BowBatch, MatchBatch,
-    InitMatchBatch, TriMatchBatch, FuseBatch, DistinctBatch)."""
+    InitMatchBatch, TriMatchBatch, FuseBatch, DistinctBatch, ScoreBatch)."""
 
     def __init__(self, library: C.CDLL, prefix: str, *create_args):
         self._L, self._prefix, self._h = library, prefix, C.c_void_p(0)

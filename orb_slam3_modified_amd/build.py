@@ -12,6 +12,7 @@ LIBS is the one place that knows them, one record per library; what is stale, wh
   liborbx_trimatch.so   the batched SearchForTriangulation (include/orbx_trimatch.h)
   liborbx_fuse.so       the batched Fuse search (include/orbx_fuse.h)
   liborbx_mpdesc.so     the batched ComputeDistinctiveDescriptors (include/orbx_mpdesc.h)
+  liborbx_score.so      the six DBoW2 scorings for two batches of BowVectors (include/orbx_score.h); takes nothing from the product
 The libraries beside the product link liborbx.so and use its ABI (and orbx_internal.h where they read a context's buffers).  Their sources sit
 in subdirectories of csrc/, outside kernels_hash(): the committed counter files measure the product's kernels, which they do not change.
 A new one is one more record ("Adding a side library")."""
@@ -44,6 +45,8 @@ FUSE_OUT = os.path.join(os.path.dirname(OUT), "liborbx_fuse.so")
 FUSE_SOURCE = os.path.join("fuse", "orbx_fuse.hip")
 MPDESC_OUT = os.path.join(os.path.dirname(OUT), "liborbx_mpdesc.so")
 MPDESC_SOURCE = os.path.join("mpdesc", "orbx_mpdesc.hip")
+SCORE_OUT = os.path.join(os.path.dirname(OUT), "liborbx_score.so")
+SCORE_SOURCE = os.path.join("score", "orbx_score.hip")
 
 
 class Lib(NamedTuple):
@@ -63,9 +66,10 @@ LIBS = (Lib(OUT, tuple(SOURCES)),
         Lib(INITMATCH_OUT, (INITMATCH_SOURCE,), hidden=True, product=True),
         Lib(TRIMATCH_OUT, (TRIMATCH_SOURCE,), hidden=True, product=True),
         Lib(FUSE_OUT, (FUSE_SOURCE,), hidden=True, product=True),
-        Lib(MPDESC_OUT, (MPDESC_SOURCE,), hidden=True, product=True))
+        Lib(MPDESC_OUT, (MPDESC_SOURCE,), hidden=True, product=True),
+        Lib(SCORE_OUT, (SCORE_SOURCE,), hidden=True))
 HEADERS = ("orbx.h", "orbx_debug.h", "orbx_train.h", "orbx_stereo.h", "orbx_bow.h", "orbx_match.h", "orbx_initmatch.h", "orbx_trimatch.h",
-           "orbx_fuse.h", "orbx_mpdesc.h")
+           "orbx_fuse.h", "orbx_mpdesc.h", "orbx_score.h")
 # -ffp-contract=off: the float paths (fastAtan2 polynomial, BRIEF rotation) must not be fused into FMAs,
 # the CPU reference evaluates them as separate IEEE operations (DESIGN.md "bit-exactness").
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall",
