@@ -22,6 +22,7 @@ TRIMATCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_trimatch.so
 FUSE_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_fuse.so")             # the batched Fuse search (include/orbx_fuse.h)
 MPDESC_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_mpdesc.so")         # the batched ComputeDistinctiveDescriptors (include/orbx_mpdesc.h)
 SCORE_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_score.so")           # the six DBoW2 scorings (include/orbx_score.h)
+FISHEYE_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_fisheye.so")       # the batched two-camera rig front-end (include/orbx_fisheye.h)
 
 ORBX_OK, ORBX_E_INVALID, ORBX_E_EMPTY, ORBX_E_DEVICE, ORBX_E_CAPACITY, ORBX_E_FORMAT = 0, -1, -2, -3, -4, -5
 NUM_KERNELS = 6
@@ -388,9 +389,28 @@ def score_lib() -> C.CDLL:
     return M
 
 
+def fisheye_lib() -> C.CDLL:
+    """liborbx_fisheye.so.  `_orbx_fisheye_symbols`: every name of include/orbx_fisheye.h, bound here with its signature."""
+    vp, i32, sz = C.c_void_p, C.c_int, C.c_size_t
+    sig = {
+        "orbx_fisheye_create": (i32, [C.POINTER(vp), vp, vp]),
+        "orbx_fisheye_destroy": (None, [vp]),
+        "orbx_fisheye_last_error": (C.c_char_p, [vp]),
+        "orbx_fisheye_match_batch_device": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "orbx_fisheye_finish_batch_device": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "orbx_fisheye_extract_batch_device": (i32, [vp, vp, vp, i32, i32, i32, sz, sz, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                    vp]),
+        "orbx_fisheye_match_batch": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "orbx_fisheye_finish_batch": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    }
+    M = _load_side(FISHEYE_LIB_PATH, sig)
+    M._orbx_fisheye_symbols = tuple(sig)
+    return M
+
+
 class SideHandle:
     """A handle of a side library whose entry points are <prefix>_create / _destroy / _last_error (StereoBatch, BowBatch, MatchBatch,
-    InitMatchBatch, TriMatchBatch, FuseBatch, DistinctBatch, ScoreBatch)."""
+    InitMatchBatch, TriMatchBatch, FuseBatch, DistinctBatch, ScoreBatch, FisheyeBatch)."""
 
     def __init__(self, library: C.CDLL, prefix: str, *create_args):
         self._L, self._prefix, self._h = library, prefix, C.c_void_p(0)

@@ -1,5 +1,5 @@
 // The device helpers the batched pair matchers share (liborbx_match.so, liborbx_initmatch.so): descriptors and Hamming distances, the wave
-// minimum, a chain's relaxed loads and stores, the rotation bin, the keypoint field reader and the LDS-DMA staging.  Device code only; it
+// minimum, the 32-bit top-2 keys (liborbx_fisheye.so), a chain's relaxed loads and stores, the rotation bin, the keypoint field reader and the LDS-DMA staging.  Device code only; it
 // sits below csrc/, outside kernels_hash().  A kernel's file imports the names with `using namespace orbx::side::dev;` inside its anonymous
 // namespace.  ComputeThreeMaxima and the trip loop's three-reduction merge stay written out in both kernels: as functions of this header
 // they change the kernels' instruction streams (the compiler unrolls and schedules them differently).
@@ -28,6 +28,21 @@ __device__ __forceinline__ int hamming(const D8& a, const D8& b) {
   for (int k = 0; k < 8; k++) s += __popc(a.w[k] ^ b.w[k]);
   return s;
 }
+
+// The two smallest (distance, train index) keys of a sequential scan, as csrc/orbx_matcher.hip's k_knn2_partial keeps them: one 32-bit key
+// distance (0 .. 256) << 22 | index (< 2^22), so that equal distances order by index and the update is three min / max instructions.
+constexpr uint32_t kNoKey32 = 0xffffffffu;
+constexpr int kKeyIndexBits = 22;
+struct Top2x32 { uint32_t k1, k2; };
+__device__ __forceinline__ Top2x32 top2_push(Top2x32 t, uint32_t dist, uint32_t index) {
+  const uint32_t key = (dist << kKeyIndexBits) | index;
+  const uint32_t hi = max(t.k1, key);
+  t.k1 = min(t.k1, key);
+  t.k2 = min(t.k2, hi);
+  return t;
+}
+__device__ __forceinline__ int key_index(uint32_t k) { return k == kNoKey32 ? -1 : (int)(k & ((1u << kKeyIndexBits) - 1u)); }
+__device__ __forceinline__ int key_dist(uint32_t k) { return k == kNoKey32 ? 256 : (int)(k >> kKeyIndexBits); }
 
 // the minimum over the 64 lanes (all active), wave-uniform: four DPP steps leave each row of 16 lanes with its minimum (lane <-> lane ^ 1,
 // lane ^ 2, mirror of the half row, mirror of the row), the four rows meet through readlane

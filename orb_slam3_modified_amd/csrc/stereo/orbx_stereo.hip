@@ -21,6 +21,7 @@
 
 #include "../orbx_internal.h"
 #include "../side/orbx_handle.h"
+#include "../side/orbx_rig.h"
 #include "../../../include/orbx_stereo.h"
 
 namespace {
@@ -306,17 +307,7 @@ namespace {
 
 using namespace orbx::side;
 
-// what makes the two extractions of a pair comparable: Frame's stereo constructor builds both extractors from one set of settings
-const char* param_mismatch(const orbx_ctx* a, const orbx_ctx* b) {
-  if (a->device != b->device) return "the two contexts live on different devices";
-  if (a->nfeatures != b->nfeatures || a->nlevels != b->nlevels || a->scale_factor != b->scale_factor || a->ini_th != b->ini_th ||
-      a->min_th != b->min_th)
-    return "the two contexts have different extractor parameters (nfeatures, levels, scale factor, FAST thresholds)";
-  if (a->gauss_kernel != b->gauss_kernel || a->gauss_round != b->gauss_round || a->gauss_tail != b->gauss_tail || a->atan_fma != b->atan_fma ||
-      a->brief_fma != b->brief_fma)
-    return "the two contexts have different CPU profiles (gauss_kernel, gauss_round, gauss_tail, atan_fma, brief_fma)";
-  return nullptr;
-}
+const char* param_mismatch(const orbx_ctx* a, const orbx_ctx* b) { return rig_mismatch(a, b); }
 
 void side_geom(const orbx_ctx* c, SbSide* s) {
   s->lv0 = c->last_imgs; s->lv0_row = (long long)c->last_row_stride; s->lv0_frame = (long long)c->last_frame_stride;
