@@ -23,6 +23,7 @@ FUSE_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_fuse.so")      
 MPDESC_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_mpdesc.so")         # the batched ComputeDistinctiveDescriptors (include/orbx_mpdesc.h)
 SCORE_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_score.so")           # the six DBoW2 scorings (include/orbx_score.h)
 FISHEYE_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_fisheye.so")       # the batched two-camera rig front-end (include/orbx_fisheye.h)
+LOCALMATCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_localmatch.so")   # the batched SearchLocalPoints (include/orbx_localmatch.h)
 
 ORBX_OK, ORBX_E_INVALID, ORBX_E_EMPTY, ORBX_E_DEVICE, ORBX_E_CAPACITY, ORBX_E_FORMAT = 0, -1, -2, -3, -4, -5
 NUM_KERNELS = 6
@@ -408,9 +409,31 @@ def fisheye_lib() -> C.CDLL:
     return M
 
 
+class OrbxLocalMatchSide(C.Structure):
+    """orbx_localmatch_side (include/orbx_localmatch.h)."""
+    _fields_ = [("d_kps", C.c_void_p), ("d_desc", C.c_void_p), ("d_counts", C.c_void_p), ("d_uright", C.c_void_p), ("d_bounds", C.c_void_p),
+                ("nframes", C.c_int), ("capacity", C.c_int)]
+
+
+def localmatch_lib(path: str = LOCALMATCH_LIB_PATH) -> C.CDLL:
+    """liborbx_localmatch.so.  `_orbx_localmatch_symbols`: every name of include/orbx_localmatch.h, bound here with its signature.  `path`: a
+    timing build of the same source (tools/localmatch_times.py)."""
+    vp, i32, f32, sp, fp = C.c_void_p, C.c_int, C.c_float, C.POINTER(OrbxLocalMatchSide), C.POINTER(C.c_float)
+    sig = {
+        "orbx_localmatch_create": (i32, [C.POINTER(vp), i32]),
+        "orbx_localmatch_destroy": (None, [vp]),
+        "orbx_localmatch_last_error": (C.c_char_p, [vp]),
+        "orbx_localmatch_search_device": (i32, [vp, sp, vp, i32, vp, vp, i32, vp, i32, fp, i32, f32, f32, vp, vp, vp, vp]),
+        "orbx_localmatch_search": (i32, [vp, sp, vp, i32, vp, vp, i32, vp, i32, fp, i32, f32, f32, vp, vp, vp]),
+    }
+    M = _load_side(path, sig)
+    M._orbx_localmatch_symbols = tuple(sig)
+    return M
+
+
 class SideHandle:
     """A handle of a side library whose entry points are <prefix>_create / _destroy / _last_error (StereoBatch, BowBatch, MatchBatch,
-    InitMatchBatch, TriMatchBatch, FuseBatch, DistinctBatch, ScoreBatch, FisheyeBatch)."""
+    InitMatchBatch, TriMatchBatch, FuseBatch, DistinctBatch, ScoreBatch, FisheyeBatch, LocalMatchBatch)."""
 
     def __init__(self, library: C.CDLL, prefix: str, *create_args):
         self._L, self._prefix, self._h = library, prefix, C.c_void_p(0)

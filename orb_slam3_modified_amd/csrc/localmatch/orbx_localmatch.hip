@@ -1,0 +1,533 @@
+// The batched SearchLocalPoints (include/orbx_localmatch.h): ORBmatcher::SearchByProjection(Frame&, const vector<MapPoint*>&, th, ...)
+// (src/ORBmatcher.cc:43-141, Nleft == -1) for B (frame, local map) items on the keypoints and descriptors a batch extraction left in HBM
+// and the map points' descriptors in the pool ComputeDistinctiveDescriptors fills.
+//
+// k_local_match<LDS>: one workgroup of 8 waves per item (a grid of at most kMaxBlocks workgroups walks the items).
+//   check, all waves     the item's frame, count, nmp and every in-view point's level and pool row, before any of them addresses memory.
+//   phase A, all waves   the frame's keypoints as keys (cell << 16 | index), sorted (bitonic, keys are unique: the order is the frame grid's:
+//                        cells x-major, then y, then ascending index), a 16-byte record {x, y, octave, uright} per sorted position, the cells'
+//                        starts by binary search.  A LANE PER MAP POINT walks its window twice (a window holds a handful of candidates, and
+//                        with a lane per point the walk order never crosses lanes): once to count, and after a workgroup scan, for a chunk of
+//                        points whose lists fit the candidate room, once to write its list with the point's descriptor in 8 registers.  A
+//                        candidate is one word: index (15 bits), Hamming distance (9), octave (5, two's complement: -1 .. 15).  The level
+//                        range, the strict window test and the stereo gate are applied here; the kp_obs test is the chain's.
+//   phase B, wave 0      the chain over the chunk's points in index order: lane j holds candidate j (+ 64 per trip), drops the entries whose
+//                        keypoint is hidden (a bit per keypoint in LDS, from the kp_obs row, set on every acceptance with obs > 0), keeps its
+//                        two smallest (distance << 15 | position) keys; two DPP min-reductions give the wave's two smallest, whose entries
+//                        carry the octaves.  The accept test is wave-uniform; one lane records the point's keypoint and sets the hidden bit.
+//                        No descriptor and no keypoint is read here.  A and B repeat per chunk: the distances do not depend on the chain,
+//                        so where the chunks are cut changes nothing.
+//   phase C, all waves   kp_match[keypoint] = the LAST accepted point that took it (an integer maximum over the points' indices: a point
+//                        with obs == 0 does not hide its keypoint, a later one may rebind it), then kp_obs[keypoint] = that point's obs.
+// LDS path: the frame's descriptors (16-byte LDS-DMA loads), the grid, the offsets, the points' results and the candidate room in LDS.
+// Global path (sizes that need more LDS than the handle's limit): the descriptors where they lie, everything else in the workgroup's slice of
+// the handle's scratch.  The hidden bits are 4 KiB of static LDS on both paths.
+// The float expressions are compiled with -ffp-contract=off: every operation is rounded by itself, as the specification states them.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstring>
+#include <string>
+
+#include "../side/orbx_handle.h"
+#include "../side/orbx_pair_device.h"
+#include "../../../include/orbx_localmatch.h"
+
+namespace {
+
+using namespace orbx::side::dev;          // ld / st on the chain's state: written by one lane, read by the wave's other lanes in the next step
+
+constexpr int kThreads = 512;             // 8 waves
+constexpr int kLdsMax = 148 * 1024;       // dynamic LDS of one workgroup (160 KiB per CU, the static part is below 8 KiB)
+constexpr int kMaxBlocks = 1024;          // workgroups of one launch on the LDS path
+constexpr int kGlobalBlocks = 256;        // ... on the global path: each owns one slice of the scratch
+constexpr int kGlobalRoom = 64 * 1024;    // candidates of one chunk on the global path (at least the capacity)
+constexpr int kMaxCap = ORBX_LOCALMATCH_MAX_CAPACITY;   // a key and a candidate hold a 15-bit index
+constexpr int kCols = 64, kRows = 48, kCells = kCols * kRows;
+constexpr int kThHigh = 100;
+constexpr int kNone = INT_MAX;            // no key
+static_assert(kMaxCap == 32768, "15-bit indices and positions");
+
+constexpr size_t kX = offsetof(orbx_keypoint, x), kY = offsetof(orbx_keypoint, y), kOctave = offsetof(orbx_keypoint, octave);
+
+struct __align__(16) Rec { float x, y; int32_t octave; float ur; };
+
+// a / b for a normal a > 0 (64 and 48 here) and any b, rounded to nearest even as the float division is, by long division of the
+// significands in integers: the division's own expansion would put fused multiply-adds into the code object.  A zero or subnormal b gives an
+// infinity (64 / b is beyond FLT_MAX for every b below 1.9e-37), an infinite b a zero, a NaN itself.
+__host__ __device__ inline float div_rn(float a, float b) {
+  uint32_t ua, ub;
+  memcpy(&ua, &a, 4); memcpy(&ub, &b, 4);
+  const uint32_t sign = ub & 0x80000000u, eb = (ub >> 23) & 0xFFu;
+  uint32_t out;
+  if (eb == 0xFFu) out = (ub & 0x7FFFFFu) ? ub : sign;
+  else if (eb == 0u) out = sign | 0x7F800000u;
+  else {
+    uint32_t ma = (ua & 0x7FFFFFu) | 0x800000u;
+    const uint32_t mb = (ub & 0x7FFFFFu) | 0x800000u;
+    int e = (int)((ua >> 23) & 0xFFu) - (int)eb;
+    if (ma < mb) { ma <<= 1; e--; }        // 1 <= ma / mb < 2
+    uint32_t rem = ma - mb, q = 1u;        // the quotient's leading bit, then 23 more and a guard bit
+#pragma unroll
+    for (int i = 0; i < 24; i++) {
+      rem <<= 1; q <<= 1;
+      if (rem >= mb) { rem -= mb; q |= 1u; }
+    }
+    uint32_t m = q >> 1;
+    if ((q & 1u) && (rem != 0u || (m & 1u))) m++;
+    if (m == 0x1000000u) { m >>= 1; e++; }
+    const int be = e + 127;                // at least 5 for a >= 48 and a normal b
+    out = be >= 255 ? sign | 0x7F800000u : be < 1 ? sign : sign | (uint32_t)be << 23 | (m & 0x7FFFFFu);
+  }
+  float r;
+  memcpy(&r, &out, 4);
+  return r;
+}
+
+struct Args {
+  const uint8_t* kps; const uint8_t* desc; const int32_t* counts; const float* uright; const float* bounds;
+  const int32_t* frames; const orbx_localmatch_point* mp; const int32_t* nmp; const uint8_t* pdesc;
+  int32_t* kp_obs; int32_t* kp_match; int32_t* nmatches;
+  uint8_t* scratch; size_t scratch_stride;
+  int nframes, cap, nitems, mcap, npoints, nlevels, p2, room, factor;
+  float th, ratio;
+  float sf[ORBX_LOCALMATCH_MAX_LEVELS];
+};
+
+// one item's arrays, as offsets in the LDS block resp. the scratch slice (16-byte aligned)
+struct Lay { size_t desc, keys, recs, cstart, offs, res, cand, fixed; };
+__host__ __device__ inline Lay layout(int cap, int mcap, int p2, bool lds) {
+  Lay l;
+  size_t o = 0;
+  auto add = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 15) & ~(size_t)15; return at; };
+  l.desc = add(lds ? (size_t)cap * 32 : 0);
+  l.keys = add((size_t)p2 * 4);             // sorted (cell << 16 | index) of the frame's keypoints
+  l.recs = add((size_t)cap * sizeof(Rec));  // their records, in the same order
+  l.cstart = add((size_t)(kCells + 1) * 2); // first sorted position of every cell
+  l.offs = add((size_t)(mcap + 1) * 4);     // first candidate of every point (exclusive scan of the counts)
+  l.res = add((size_t)mcap * 4);            // the keypoint a point was accepted with, -1 without
+  l.cand = o;
+  l.fixed = o;
+  return l;
+}
+
+// Frame::GetFeaturesInArea(x, y, r, level - 1, level) (src/Frame.cc:657-723) over the sorted records: emit(record) for every candidate, in
+// the reference's order.  level >= 0, so bCheckLevels holds and both bounds are tested.
+template <class F>
+__device__ __forceinline__ void walk(float minX, float minY, float invW, float invH, float x, float y, float r, int level, const uint16_t* cstart,
+                                     const Rec* recs, const uint32_t* keys, F emit) {
+  const int x0 = max(0, (int)floorf((x - minX - r) * invW));
+  if (x0 >= kCols) return;
+  const int x1 = min(kCols - 1, (int)ceilf((x - minX + r) * invW));
+  if (x1 < 0) return;
+  const int y0 = max(0, (int)floorf((y - minY - r) * invH));
+  if (y0 >= kRows) return;
+  const int y1 = min(kRows - 1, (int)ceilf((y - minY + r) * invH));
+  if (y1 < 0) return;
+  if (y1 < y0) return;                     // an empty range of rows (the reference's inner loop does not run)
+  for (int ix = x0; ix <= x1; ix++) {      // the cells (ix, y0 .. y1) are neighbours in the sorted keys
+    const int j1 = cstart[ix * kRows + y1 + 1];
+    for (int j = cstart[ix * kRows + y0]; j < j1; j++) {
+      const Rec c = recs[j];
+      if (c.octave < level - 1 || c.octave > level) continue;
+      if (fabsf(c.x - x) < r && fabsf(c.y - y) < r) emit(c, (int)(keys[j] & 0xFFFFu));
+    }
+  }
+}
+
+// a point's window: RadiusByViewingCos (src/ORBmatcher.cc:214-220), th, the level's scale
+struct Pt { float x, y, xr, radius; int level, point; bool live; };
+__device__ __forceinline__ Pt load_point(const orbx_localmatch_point* p, const float* s_sf, float th, int factor) {
+  const uint4* const rp = (const uint4*)p;
+  const uint4 lo = rp[0], hi = rp[1];
+  Pt t;
+  t.x = __uint_as_float(lo.x); t.y = __uint_as_float(lo.y); t.xr = __uint_as_float(lo.z);
+  const float vc = __uint_as_float(lo.w);
+  t.level = (int)hi.x; t.point = (int)hi.z;
+  // in view, and finite: a NaN fails every comparison (the reference leaves a non-finite projection undefined; here it has no candidate)
+  t.live = hi.w != 0u && fabsf(t.x) < INFINITY && fabsf(t.y) < INFINITY && fabsf(vc) < INFINITY;
+  t.radius = 0.0f;
+  if (t.live) {                            // the level is one of the table's: the check
+    float r = ((double)vc > 0.998) ? 2.5f : 4.0f;
+    if (factor) r *= th;
+    t.radius = r * s_sf[t.level];
+  }
+  return t;
+}
+
+template <bool LDS>
+__global__ __launch_bounds__(kThreads) void k_local_match(Args g) {
+  extern __shared__ __align__(16) uint8_t smem[];
+  __shared__ int s_cnt, s_bad;
+  __shared__ int s_scan[kThreads];
+  __shared__ int32_t s_hidden[kMaxCap / 32];   // bit i: keypoint i holds a map point with Observations() > 0
+  __shared__ float s_sf[ORBX_LOCALMATCH_MAX_LEVELS];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int cap = g.cap, mcap = g.mcap;
+  const Lay L = layout(cap, mcap, g.p2, LDS);
+  uint8_t* const base = LDS ? smem : g.scratch + (size_t)blockIdx.x * g.scratch_stride;
+  uint32_t* const keys = (uint32_t*)(base + L.keys);
+  Rec* const recs = (Rec*)(base + L.recs);
+  uint16_t* const cstart = (uint16_t*)(base + L.cstart);
+  int32_t* const offs = (int32_t*)(base + L.offs);
+  int32_t* const res = (int32_t*)(base + L.res);
+  uint32_t* const cand = (uint32_t*)(base + L.cand);
+
+  if (tid < ORBX_LOCALMATCH_MAX_LEVELS) {  // the level table: constant indices into the kernel's arguments
+    float v = 0.0f;
+#pragma unroll
+    for (int l = 0; l < ORBX_LOCALMATCH_MAX_LEVELS; l++)
+      if (tid == l) v = g.sf[l];
+    s_sf[tid] = v;
+  }
+
+  for (int b = blockIdx.x; b < g.nitems; b += gridDim.x) {
+    __syncthreads();                       // the previous item's shared state has been read
+    int32_t* const omatch = g.kp_match + (size_t)b * cap;
+    int32_t* const oobs = g.kp_obs + (size_t)b * cap;
+    const orbx_localmatch_point* const mp = g.mp + (size_t)b * mcap;
+    // ---- the check: nothing below addresses memory with a value that was not tested here
+    const int f = g.frames[b], nmp = g.nmp[b];
+    bool ok = f >= 0 && f < g.nframes && nmp >= 0 && nmp <= mcap;
+    int n = 0;
+    if (ok) {
+      n = g.counts[2 * f];
+      ok = n >= 0 && n <= cap;
+    }
+    if (tid == 0) { s_cnt = 0; s_bad = 0; }
+    for (int i = tid; i < cap; i += kThreads) omatch[i] = -1;
+    __syncthreads();
+    if (ok) {                              // uniform over the workgroup
+      bool bad = false;
+      for (int q = tid; q < nmp; q += kThreads) {
+        const uint4 hi = ((const uint4*)(mp + q))[1];
+        bad |= hi.w != 0u && ((int)hi.x < 0 || (int)hi.x >= g.nlevels || (int)hi.z < 0 || (int)hi.z >= g.npoints);
+      }
+      if (bad) s_bad = 1;
+    }
+    __syncthreads();
+    if (!ok || s_bad) {                    // uniform over the workgroup: a row of -1, kp_obs as it was
+      if (tid == 0) g.nmatches[b] = -1;
+      continue;
+    }
+    const size_t of = (size_t)f * cap;
+    const uint8_t* const kp = g.kps + of * sizeof(orbx_keypoint);
+    const float* const ur = g.uright ? g.uright + of : nullptr;
+    const uint8_t* const desc = LDS ? base + L.desc : g.desc + of * 32;
+    const float minX = g.bounds[4 * f], minY = g.bounds[4 * f + 1];
+    const float invW = div_rn((float)kCols, g.bounds[4 * f + 2] - minX), invH = div_rn((float)kRows, g.bounds[4 * f + 3] - minY);   // src/Frame.cc:153-160
+
+    // ---- phase A: the frame's grid
+    if (LDS) stage_dma<kThreads>(base + L.desc, g.desc + of * 32, n * 2);
+    for (int w = tid; w < kMaxCap / 32; w += kThreads) s_hidden[w] = 0;
+    for (int q = tid; q < nmp; q += kThreads) res[q] = -1;
+    __syncthreads();
+    for (int i = tid; i < n; i += kThreads) {
+      if (oobs[i] > 0) atomicOr(&s_hidden[i >> 5], (int)(1u << (i & 31)));
+      // Frame::PosInGrid (src/Frame.cc:725-735)
+      const float fx = roundf((kp_field<float>(kp, i, kX) - minX) * invW), fy = roundf((kp_field<float>(kp, i, kY) - minY) * invH);
+      if (!(fx >= 0.0f && fx < (float)kCols && fy >= 0.0f && fy < (float)kRows)) continue;   // outside the grid (or NaN): in no cell
+      const int k = atomicAdd(&s_cnt, 1);  // k < n <= cap <= p2
+      keys[k] = (uint32_t)((int)fx * kRows + (int)fy) << 16 | (uint32_t)i;
+    }
+    __syncthreads();
+    const int n0 = s_cnt;                  // the frame's keypoints inside the grid
+    int n2 = 2;
+    while (n2 < n0) n2 <<= 1;              // n2 <= p2
+    for (int i = n0 + tid; i < n2; i += kThreads) keys[i] = 0xFFFFFFFFu;
+    __syncthreads();
+    for (int k = 2; k <= n2; k <<= 1)
+      for (int j = k >> 1; j > 0; j >>= 1) {
+        for (int t = tid; t < (n2 >> 1); t += kThreads) {
+          const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
+          const uint32_t a = keys[i], c = keys[l];
+          if ((a > c) == ((i & k) == 0)) { keys[i] = c; keys[l] = a; }
+        }
+        __syncthreads();
+      }
+    for (int j = tid; j < n0; j += kThreads) {
+      const size_t i = keys[j] & 0xFFFFu;
+      recs[j] = Rec{kp_field<float>(kp, i, kX), kp_field<float>(kp, i, kY), kp_field<int32_t>(kp, i, kOctave), ur ? ur[i] : -1.0f};
+    }
+    for (int c = tid; c <= kCells; c += kThreads) {
+      const uint32_t want = (uint32_t)c << 16;
+      int lo = 0, hi = n0;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (keys[mid] < want) lo = mid + 1; else hi = mid;
+      }
+      cstart[c] = (uint16_t)lo;            // <= 32768
+    }
+    __syncthreads();
+
+    // ---- phase A: every point's candidate count, then the offsets
+    for (int q = tid; q <= nmp; q += kThreads) {
+      int c = 0;
+      if (q < nmp) {
+        const Pt t = load_point(mp + q, s_sf, g.th, g.factor);
+        if (t.live)
+          walk(minX, minY, invW, invH, t.x, t.y, t.radius, t.level, cstart, recs, keys, [&](const Rec& r, int) {
+            if (r.ur > 0.0f && fabsf(t.xr - r.ur) > t.radius) return;   // the stereo gate, src/ORBmatcher.cc:96-101
+            c++;
+          });
+      }
+      offs[q] = c;
+    }
+    __syncthreads();
+    {
+      const int m = nmp + 1, per = (m + kThreads - 1) / kThreads;
+      const int lo = min(m, tid * per), hi = min(m, lo + per);
+      int s = 0;
+      for (int i = lo; i < hi; i++) s += offs[i];
+      s_scan[tid] = s;
+      __syncthreads();
+      for (int d = 1; d < kThreads; d <<= 1) {
+        const int v = tid >= d ? s_scan[tid - d] : 0;
+        __syncthreads();
+        s_scan[tid] += v;
+        __syncthreads();
+      }
+      int run = s_scan[tid] - s;
+      for (int i = lo; i < hi; i++) { const int c = offs[i]; offs[i] = run; run += c; }
+    }
+    if (LDS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the LDS-DMA loads have landed
+    __syncthreads();
+
+    // ---- chunks of points whose candidates fit the room: lists with distances (all waves), then the chain (wave 0)
+    int nm = 0;                            // wave 0's count of acceptances
+    for (int q0 = 0; q0 < nmp;) {
+      const int e0 = offs[q0];
+      int q1;
+      {                                    // the largest q1 with offs[q1] - e0 <= room; one point's list (<= cap <= room) always fits
+        int lo = q0 + 1, hi = nmp;
+        while (lo < hi) {
+          const int mid = (lo + hi + 1) >> 1;
+          if (offs[mid] - e0 <= g.room) lo = mid; else hi = mid - 1;
+        }
+        q1 = lo;
+      }
+      const int tot = min(offs[q1] - e0, g.room);
+      for (int q = q0 + tid; q < q1; q += kThreads) {
+        int k = offs[q] - e0;
+        const int kend = offs[q + 1] - e0;
+        if (kend > k) {
+          const Pt t = load_point(mp + q, s_sf, g.th, g.factor);
+          const D8 qd = load_desc(g.pdesc + (size_t)t.point * 32);   // the pool row is below npoints: the check
+          walk(minX, minY, invW, invH, t.x, t.y, t.radius, t.level, cstart, recs, keys, [&](const Rec& r, int i) {
+            if (r.ur > 0.0f && fabsf(t.xr - r.ur) > t.radius) return;
+            if (k < kend && k < tot) {
+              const int d = hamming(qd, load_desc(desc + (size_t)i * 32));
+              cand[k] = (uint32_t)i | (uint32_t)d << 15 | ((uint32_t)r.octave & 31u) << 24;
+            }
+            k++;
+          });
+        }
+      }
+      __syncthreads();
+
+#ifndef ORBX_LOCALMATCH_NO_CHAIN          // (a timing build without phase B: tools/localmatch_times.py; its results are not the specification's)
+      if (tid < 64) {                      // ---- phase B
+        for (int c0 = q0; c0 < q1; c0 += 64) {
+          const int cn = min(64, q1 - c0);
+          int l_b = 0, l_n = 0, l_obs = 0;
+          if (lane < cn) {
+            l_b = offs[c0 + lane] - e0; l_n = offs[c0 + lane + 1] - e0 - l_b;
+            l_obs = mp[c0 + lane].obs;
+          }
+          for (int i = 0; i < cn; i++) {
+            const int cnt = __builtin_amdgcn_readlane(l_n, i);
+            if (cnt <= 0) continue;
+            const int b0 = __builtin_amdgcn_readlane(l_b, i);
+            int k1 = kNone, k2 = kNone;    // the lane's two smallest (distance << 15 | position)
+            for (int j = lane; j < cnt; j += 64) {
+              const uint32_t e = cand[b0 + j];
+              const int idx = (int)(e & 0x7FFFu);
+              if ((ld(s_hidden + (idx >> 5)) >> (idx & 31)) & 1) continue;
+              const int key = (int)((e >> 15) & 0x1FFu) << 15 | j;
+              const int hi = max(k1, key);
+              k1 = min(k1, key);
+              k2 = min(k2, hi);
+            }
+            const int m1 = wave_min(k1);
+            if (m1 == kNone || (m1 >> 15) > kThHigh) continue;
+            const int m2 = wave_min(k1 == m1 ? k2 : k1);   // positions are unique: one lane holds m1
+            const uint32_t e1 = cand[b0 + (m1 & 0x7FFF)];
+            const int best = m1 >> 15, level1 = (int)(e1 >> 24 & 31u);
+            int second = 256, level2 = 31; // bestDist2 = 256, bestLevel2 = -1
+            if (m2 != kNone) {
+              second = m2 >> 15;
+              level2 = (int)(cand[b0 + (m2 & 0x7FFF)] >> 24 & 31u);
+            }
+            // :117-130: dropped when the levels agree and bestDist > mfNNratio * bestDist2, kept when they differ or bestDist <= ...
+            if (level1 != level2 || (float)best <= g.ratio * (float)second) {
+              const int obs = __builtin_amdgcn_readlane(l_obs, i);
+              if (lane == 0) {
+                const int idx = (int)(e1 & 0x7FFFu);
+                st(res + c0 + i, idx);
+                if (obs > 0) st(s_hidden + (idx >> 5), ld(s_hidden + (idx >> 5)) | (int)(1u << (idx & 31)));
+              }
+              nm++;
+              __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // the stores are done before the next point's loads
+            }
+          }
+        }
+      }
+#endif
+      __syncthreads();
+      q0 = q1;
+    }
+
+    // ---- phase C: the last point that took a keypoint holds it; integer maxima, so the order does not matter
+    for (int q = tid; q < nmp; q += kThreads) {
+      const int i = res[q];
+      if (i >= 0 && i < n) __hip_atomic_fetch_max(omatch + i, q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    for (int i = tid; i < n; i += kThreads) {
+      const int q = __hip_atomic_load(omatch + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (q >= 0 && q < nmp) oobs[i] = mp[q].obs;
+    }
+    if (tid == 0) g.nmatches[b] = nm;
+  }
+}
+
+}  // namespace
+
+struct orbx_localmatch : orbx::side::Handle {  // scratch: per workgroup the global path's arrays
+  int lds_limit = kLdsMax;                     // ORBX_LOCALMATCH_LDS at create
+};
+
+namespace {
+
+using namespace orbx::side;
+
+const char* side_problem(const orbx_localmatch_side* s) {
+  if (!s) return "null side";
+  if (s->nframes < 1 || s->capacity < 1) return "nframes and capacity must be at least 1";
+  if (s->capacity > kMaxCap) return "capacity above 32768";
+  if (!s->d_kps || !s->d_desc || !s->d_counts || !s->d_bounds) return "null buffer in the side";
+  if ((long long)s->nframes * s->capacity > (long long)INT_MAX) return "nframes * capacity exceeds INT_MAX";
+  return nullptr;
+}
+
+// what both forms check before anything is copied or launched
+int check_call(orbx_localmatch* m, const char* who, const orbx_localmatch_side* side, const void* frames, int nitems, const void* mp,
+               const void* nmp, int mcap, const void* pdesc, int npoints, const float* sf, int nlevels, float th, const void* kp_obs,
+               const void* kp_match, const void* nmatches) {
+  if (const char* e = side_problem(side)) return fail(m, ORBX_E_INVALID, std::string(who) + e);
+  if (!frames || !mp || !nmp || !pdesc) return fail(m, ORBX_E_INVALID, std::string(who) + "null frames, map points, nmp or pdesc");
+  if (!kp_obs || !kp_match || !nmatches) return fail(m, ORBX_E_INVALID, std::string(who) + "null kp_obs, kp_match or nmatches");
+  if (nitems < 1 || mcap < 1 || npoints < 1) return fail(m, ORBX_E_INVALID, std::string(who) + "nitems, mcap and npoints must be at least 1");
+  if (!sf || nlevels < 1 || nlevels > ORBX_LOCALMATCH_MAX_LEVELS)
+    return fail(m, ORBX_E_INVALID, std::string(who) + "scale_factors and nlevels in 1 .. 16 are needed (nlevels = " + std::to_string(nlevels) + ")");
+  if (!std::isfinite(th)) return fail(m, ORBX_E_INVALID, std::string(who) + "th must be finite");
+  if ((long long)mcap * side->capacity > (long long)INT_MAX || (long long)nitems * std::max(mcap, side->capacity) > (long long)INT_MAX)
+    return fail(m, ORBX_E_INVALID, std::string(who) + "mcap * capacity or nitems * max(mcap, capacity) exceeds INT_MAX");
+  return ORBX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int orbx_localmatch_create(orbx_localmatch** out, int device) {
+  if (out) *out = nullptr;
+  if (!out) return create_fail(ORBX_E_INVALID, "orbx_localmatch_create", "null argument");
+  if (device < 0) return create_fail(ORBX_E_INVALID, "orbx_localmatch_create", "device must be >= 0");
+  orbx_localmatch* m = new orbx_localmatch();
+  m->lds_limit = env_int("ORBX_LOCALMATCH_LDS", 0, kLdsMax, kLdsMax);
+  const char* e = open_handle(m, device);
+  if (!e) e = allow_lds((const void*)k_local_match<true>, kLdsMax);
+  if (e) { orbx_localmatch_destroy(m); return create_fail(ORBX_E_DEVICE, "orbx_localmatch_create", e); }
+  *out = m;
+  return ORBX_OK;
+}
+
+void orbx_localmatch_destroy(orbx_localmatch* m) {
+  if (!m) return;
+  close_handle(m);
+  delete m;
+}
+
+const char* orbx_localmatch_last_error(const orbx_localmatch* m) { return last_error(m); }
+
+int orbx_localmatch_search_device(orbx_localmatch* m, const orbx_localmatch_side* side, const int32_t* d_frames, int nitems,
+                                  const orbx_localmatch_point* d_mp, const int32_t* d_nmp, int mcap, const uint8_t* d_pdesc, int npoints,
+                                  const float* scale_factors, int nlevels, float th, float nn_ratio, int32_t* d_kp_obs, int32_t* d_kp_match,
+                                  int32_t* d_nmatches, void* stream) {
+  if (!m) return ORBX_E_INVALID;
+  const char* who = "orbx_localmatch_search_device: ";
+  int rc = check_call(m, who, side, d_frames, nitems, d_mp, d_nmp, mcap, d_pdesc, npoints, scale_factors, nlevels, th, d_kp_obs, d_kp_match,
+                      d_nmatches);
+  if (rc != ORBX_OK) return rc;
+  if (((uintptr_t)side->d_desc | (uintptr_t)d_mp | (uintptr_t)d_pdesc) & 15)
+    return fail(m, ORBX_E_INVALID, std::string(who) + "d_desc, d_mp and d_pdesc must be 16-byte aligned");
+  rc = same_device(m, who, {side->d_kps, side->d_desc, side->d_counts, side->d_uright, side->d_bounds, d_frames, d_mp, d_nmp, d_pdesc, d_kp_obs,
+                            d_kp_match, d_nmatches}, "the handle");
+  if (rc != ORBX_OK) return rc;
+  ORBX_SIDE_HIP(m, hipSetDevice(m->device));
+  const int cap = side->capacity;
+  int p2 = 2;
+  while (p2 < cap) p2 <<= 1;
+  // the LDS path needs its arrays and room for one point's longest list (cap candidates); what is left of the limit is candidate room
+  const size_t fixed = layout(cap, mcap, p2, true).fixed;
+  const size_t lds_limit = (size_t)m->lds_limit & ~(size_t)15;
+  const bool in_lds = fixed + 4 * (size_t)cap <= lds_limit;
+  Args g;
+  g.kps = (const uint8_t*)side->d_kps; g.desc = side->d_desc; g.counts = side->d_counts; g.uright = side->d_uright; g.bounds = side->d_bounds;
+  g.frames = d_frames; g.mp = d_mp; g.nmp = d_nmp; g.pdesc = d_pdesc;
+  g.kp_obs = d_kp_obs; g.kp_match = d_kp_match; g.nmatches = d_nmatches;
+  g.scratch = nullptr; g.scratch_stride = 0;
+  g.nframes = side->nframes; g.cap = cap; g.nitems = nitems; g.mcap = mcap; g.npoints = npoints; g.nlevels = nlevels; g.p2 = p2;
+  g.factor = (double)th != 1.0;            // bFactor, src/ORBmatcher.cc:48
+  g.th = th; g.ratio = nn_ratio;
+  for (int l = 0; l < ORBX_LOCALMATCH_MAX_LEVELS; l++) g.sf[l] = l < nlevels ? scale_factors[l] : 0.0f;
+  size_t lds = 0;
+  int blocks;
+  if (in_lds) {
+    lds = lds_limit;
+    g.room = (int)((lds - fixed) / 4);
+    blocks = std::min(nitems, kMaxBlocks);
+  } else {
+    g.room = std::max(cap, kGlobalRoom);
+    blocks = std::min(nitems, kGlobalBlocks);
+    g.scratch_stride = (layout(cap, mcap, p2, false).fixed + 4 * (size_t)g.room + 255) & ~(size_t)255;
+    if ((rc = grow(m, &m->scratch, g.scratch_stride * blocks)) != ORBX_OK) return rc;
+    g.scratch = m->scratch.p;
+  }
+  hipStream_t st = stream ? (hipStream_t)stream : m->st;
+  if ((rc = wait_previous(m, st)) != ORBX_OK) return rc;
+  if (in_lds) hipLaunchKernelGGL(k_local_match<true>, dim3((unsigned)blocks), dim3(kThreads), lds, st, g);
+  else hipLaunchKernelGGL(k_local_match<false>, dim3((unsigned)blocks), dim3(kThreads), 0, st, g);
+  return record_call(m, st);
+}
+
+int orbx_localmatch_search(orbx_localmatch* m, const orbx_localmatch_side* side, const int32_t* frames, int nitems,
+                           const orbx_localmatch_point* mp, const int32_t* nmp, int mcap, const uint8_t* pdesc, int npoints,
+                           const float* scale_factors, int nlevels, float th, float nn_ratio, int32_t* kp_obs, int32_t* kp_match,
+                           int32_t* nmatches) {
+  if (!m) return ORBX_E_INVALID;
+  const char* who = "orbx_localmatch_search: ";
+  int rc = check_call(m, who, side, frames, nitems, mp, nmp, mcap, pdesc, npoints, scale_factors, nlevels, th, kp_obs, kp_match, nmatches);
+  if (rc != ORBX_OK) return rc;
+  Stager io;
+  const size_t nf = (size_t)side->nframes, nk = nf * side->capacity, rows = (size_t)nitems * side->capacity;
+  const size_t o_kps = io.in(side->d_kps, nk * sizeof(orbx_keypoint)), o_desc = io.in(side->d_desc, nk * 32), o_counts = io.in(side->d_counts, nf * 8);
+  const size_t o_ur = side->d_uright ? io.in(side->d_uright, nk * 4) : 0, o_bounds = io.in(side->d_bounds, nf * 16);
+  const size_t o_frames = io.in(frames, (size_t)nitems * 4), o_mp = io.in(mp, (size_t)nitems * mcap * sizeof(orbx_localmatch_point));
+  const size_t o_nmp = io.in(nmp, (size_t)nitems * 4), o_pdesc = io.in(pdesc, (size_t)npoints * 32);
+  const size_t o_obs = io.out(kp_obs, rows * 4, true), o_match = io.out(kp_match, rows * 4), o_nm = io.out(nmatches, (size_t)nitems * 4);
+  if ((rc = upload(m, io)) != ORBX_OK) return rc;
+  uint8_t* const d = m->io.p;
+  const orbx_localmatch_side ds = {(const orbx_keypoint*)(d + o_kps), d + o_desc, (const int32_t*)(d + o_counts),
+                                   side->d_uright ? (const float*)(d + o_ur) : nullptr, (const float*)(d + o_bounds), side->nframes, side->capacity};
+  rc = orbx_localmatch_search_device(m, &ds, (const int32_t*)(d + o_frames), nitems, (const orbx_localmatch_point*)(d + o_mp),
+                                     (const int32_t*)(d + o_nmp), mcap, d + o_pdesc, npoints, scale_factors, nlevels, th, nn_ratio,
+                                     (int32_t*)(d + o_obs), (int32_t*)(d + o_match), (int32_t*)(d + o_nm), m->st);
+  if (rc != ORBX_OK) return rc;
+  return download(m, io);
+}
+
+}  // extern "C"
