@@ -1,6 +1,7 @@
 """The batched SearchForInitialization (liborbx_initmatch.so, orb_slam3_modified_amd/initmatch.py) on the GPU: for every pair
 (nmatches, matches12, prev row) equal the oracle's ORBmatcher::SearchForInitialization and the per-pair orbx_search_for_initialization, on the
-buffers a batch extraction left in HBM.  All comparisons are exact."""
+buffers a batch extraction left in HBM, and on the constructed batch of tests/initmatch_cases.py (every planted edge of the header, on every
+path).  All comparisons are exact."""
 import ctypes as C
 from types import SimpleNamespace
 
@@ -318,3 +319,98 @@ def test_a_call_is_ordered_after_the_extraction_on_its_stream():
     for i, (ia, ib) in enumerate(pairs.tolist()):
         assert _check_pair(got, i, None, bt, ia, bt, ib, bounds, 100, 0.9, True, ("ordered", i)) > 0
     mb.close()
+
+
+# ---- the constructed batch of tests/initmatch_cases.py: every planted edge through the kernel, whole rows, on every path
+from tests import initmatch_cases as ic  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def constructed():
+    """The batch and -- computed once -- the model's whole rows (nmatches, matches12, matches21, prev) of every run, with and without
+    check_orientation and prev_xy.  A malformed pair: -1, rows of -1, its prev rows as they came."""
+    c = ic.build()
+    P = len(ic.PAIRS)
+    for run, (window, ratio, bounds) in ic.RUNS.items():
+        for ori in (True, False):
+            for given in (True, False):
+                n, m12, m21 = np.full(P, -1, np.int32), np.full((P, ic.CAP), -1, np.int32), np.full((P, ic.CAP), -1, np.int32)
+                prev = c["prev"].copy()
+                for p, (ia, ib) in enumerate(ic.PAIRS.tolist()):
+                    if p in ic.MALFORMED:
+                        continue
+                    (k1, d1), (k2, d2) = ic.frame(c, ia), ic.frame(c, ib)
+                    n[p], row, pv = im.search_for_initialization(k1, d1, k2, d2, bounds, prev[p, :len(k1)] if given else None, window, ratio, ori)
+                    m12[p, :len(k1)], m21[p, :len(k2)] = row, im.invert(row, len(k2))
+                    if given:
+                        prev[p, :len(k1)] = pv
+                c["want", run, ori, given] = (n, m12, m21, prev if given else None)
+    return c
+
+
+def _rows_equal(got, want, where):
+    for g, w, name in zip(got, want, ("nmatches", "matches12", "matches21", "prev_xy")):
+        assert (g is None) == (w is None), (where, name)
+        if w is not None:
+            bad = np.nonzero((np.asarray(g).view(np.int32) != np.asarray(w).view(np.int32)).reshape(len(w), -1).any(1))[0]
+            assert len(bad) == 0, (where, name, bad.tolist())
+
+
+@pytest.mark.parametrize("lds", (None, 0, lds_bytes(ic.CAP, ic.CAP)), ids=("lds", "global", "chunks"))
+def test_constructed_batch_through_the_host_form(constructed, monkeypatch, lds):
+    """Every run of the constructed batch, with and without prev_xy and check_orientation, through InitMatchBatch.pairs; matches21 = NULL
+    through the device form.  "chunks": the room is one longest list, the planted steal crosses a chunk boundary."""
+    c = constructed
+    assert lds_bytes(ic.CAP, ic.CAP) <= LDS_MAX
+    if lds is not None:
+        monkeypatch.setenv("ORBX_INITMATCH_LDS", str(lds))
+    mb = InitMatchBatch(0)
+    monkeypatch.delenv("ORBX_INITMATCH_LDS", raising=False)
+    hs = InitSide(c["kps"], c["desc"], c["counts"], ic.K, ic.CAP)
+    kept = c["prev"].copy()
+    for run, (window, ratio, bounds) in ic.RUNS.items():
+        for ori in (True, False):
+            for given in (True, False):
+                r = mb.pairs(hs, hs, ic.PAIRS, bounds, window, ratio, ori, prev_xy=c["prev"] if given else None)
+                want = c["want", run, ori, given]
+                _rows_equal((r.nmatches, r.matches12, r.matches21, r.prev_xy), want, (lds, run, ori, given))
+                for name, (p, crun, w_prev, w_none) in ic.CLAIMS.items():      # the named outcomes, read off the kernel's rows
+                    if crun == run and (ori or p not in (ic.P_ROTA, ic.P_ROTB)):
+                        w = w_prev if given else w_none
+                        assert r.matches12[p, ic.PLANTED[name]] == (-1 if w is None else ic.KP[w]), (lds, name, ori, given)
+                for p in ic.MALFORMED:
+                    assert r.nmatches[p] == -1 and (r.matches12[p] == -1).all() and (r.matches21[p] == -1).all(), p
+                    assert not given or r.prev_xy[p].tobytes() == kept[p].tobytes(), p
+    assert c["prev"].tobytes() == kept.tobytes()                  # the host form copies prev_xy: the caller's rows stay
+    # matches21 = NULL, on the device form
+    s = torch.cuda.Stream(device=dev())
+    ds = InitSide(*(torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(ic.K, ic.CAP, -1) if a.dtype.names else a).to(dev())
+                    for a in (c["kps"], c["desc"], c["counts"])), ic.K, ic.CAP)
+    for run, ori, given in (("main", True, True), ("high", False, False)):
+        window, ratio, bounds = ic.RUNS[run]
+        got = _run(mb, ds, ds, ic.PAIRS, bounds, window, ratio, ori, c["prev"] if given else None, s, m21=False)
+        n, m12, _, prev = c["want", run, ori, given]
+        _rows_equal(got, (n, m12, None, prev), (lds, run, "matches21 NULL"))
+    mb.close()
+
+
+def test_constructed_pairs_through_the_per_pair_entry_point(constructed):
+    """Every well-formed pair with keypoints on both sides through orbx_search_for_initialization (ORBmatcher.SearchForInitialization):
+    the per-frame kernel at the same edges.  The one negative-octave query goes in as octave 1 (ic.reference_view)."""
+    c = constructed
+    ex = ORBextractor(*EUROC[2], device_id=0)
+    done = 0
+    for run, (window, ratio, bounds) in ic.RUNS.items():
+        for ori in (True, False):
+            m = ORBmatcher(ex, ratio, ori)
+            n, m12, _, prev = c["want", run, ori, True]
+            for p, (ia, ib) in enumerate(ic.PAIRS.tolist()):
+                if p in ic.MALFORMED or c["counts"][ia, 0] == 0 or c["counts"][ib, 0] == 0:
+                    continue
+                (k1, d1), (k2, d2) = ic.frame(c, ia), ic.frame(c, ib)
+                pv = c["prev"][p, :len(k1)].copy()
+                sn, sm12 = m.SearchForInitialization(SimpleNamespace(mvKeysUn=ic.reference_view(k1), mDescriptors=d1, bounds=bounds),
+                                                     SimpleNamespace(mvKeysUn=k2, mDescriptors=d2, bounds=bounds), pv, window)
+                assert sn == n[p] and np.array_equal(sm12, m12[p, :len(k1)]) and pv.tobytes() == prev[p, :len(k1)].tobytes(), (run, ori, p)
+                done += 1
+    assert done == len(ic.RUNS) * 2 * (len(ic.PAIRS) - len(ic.MALFORMED) - 2)

@@ -1,6 +1,7 @@
 """The batched SearchByBoW (liborbx_match.so, orb_slam3_modified_amd/match.py) on the GPU: for every pair the matches equal the oracle's
 ORBmatcher::SearchByBoW and the per-pair orbx_search_by_bow (frame mode) resp. tests/match_batch_model.py (keyframe mode), on the buffers a
-batch extraction and BowBatch.transform_device left in HBM."""
+batch extraction and BowBatch.transform_device left in HBM, and on the constructed batch of tests/match_batch_cases.py (hand-written
+FeatureVectors, every planted node on every path)."""
 import ctypes as C
 
 import numpy as np
@@ -329,3 +330,78 @@ def test_two_calls_back_to_back_on_two_streams(euroc, monkeypatch):
     for r, w in ((r1, w1), (r2, w2)):
         assert np.array_equal(r.nmatches.cpu().numpy(), w[0]) and np.array_equal(r.b2a.cpu().numpy(), w[1]) and np.array_equal(r.a2b.cpu().numpy(), w[2])
     mb.close()
+
+
+# ---- the constructed batch of tests/match_batch_cases.py: every planted node through the kernel, whole rows, on every path
+from tests import match_batch_cases as mc  # noqa: E402
+
+MC_COMBOS = [(mode, valid, ori) for mode in (FRAME, KEYFRAMES) for valid in (True, False) for ori in (True, False)]
+MC_PATHS = {"default": {}, "global": {"ORBX_MATCH_LDS": "0"}, "trips": {"ORBX_MATCH_WAVE_NODE": "3"},
+            "global trips": {"ORBX_MATCH_LDS": "0", "ORBX_MATCH_WAVE_NODE": "0"}}
+
+
+@pytest.fixture(scope="module")
+def constructed():
+    """The batch and -- computed once -- the model's whole rows (nmatches, b2a, a2b) under every run, mode, valid form and
+    check_orientation.  A malformed pair: -1 and rows of -1."""
+    c = mc.build()
+    P = len(mc.PAIRS)
+    for run, ratio in mc.RUNS.items():
+        for mode, valid, ori in MC_COMBOS:
+            n, b2a, a2b = np.full(P, -1, np.int32), np.full((P, mc.CAP), -1, np.int32), np.full((P, mc.CAP), -1, np.int32)
+            for p, (ia, ib) in enumerate(mc.PAIRS.tolist()):
+                if p in mc.MALFORMED:
+                    continue
+                (da, aa, va, fa), (db, ab, vb, fb) = mc.frame(c, ia), mc.frame(c, ib)
+                n[p], row = mm.search_by_bow(da, aa, va if valid else None, fa, db, ab, vb if valid else None, fb, mode, ratio, ori)
+                b2a[p, :len(db)], a2b[p, :len(da)] = row, mm.invert(row, len(da))
+            c["want", run, mode, valid, ori] = (n, b2a, a2b)
+    return c
+
+
+@pytest.mark.parametrize("path", list(MC_PATHS))
+def test_constructed_batch_through_the_host_form(constructed, monkeypatch, path):
+    """Both modes, both forms of `valid`, with and without check_orientation, every nn_ratio of the batch, through MatchBatch.bow_pairs.
+    "trips" and "global trips" put the 63- and 64-candidate nodes (and every smaller one) through the trip loop."""
+    c = constructed
+    for k_, v_ in MC_PATHS[path].items():
+        monkeypatch.setenv(k_, v_)
+    mb = MatchBatch(0)
+    for k_ in MC_PATHS[path]:
+        monkeypatch.delenv(k_)
+    for run, ratio in mc.RUNS.items():
+        for mode, valid, ori in MC_COMBOS:
+            side = MatchSide(c["kps"], c["desc"], c["counts"], c["fv_node"], c["fv_ptr"], c["fv_feat"], c["fv_n"], mc.K, mc.CAP, c["valid"] if valid else None)
+            r = mb.bow_pairs(side, side, mc.PAIRS, mode, ratio, ori)
+            for g, w, name in zip((r.nmatches, r.b2a, r.a2b), c["want", run, mode, valid, ori], ("nmatches", "b2a", "a2b")):
+                bad = np.nonzero((g != w).reshape(len(w), -1).any(1))[0]
+                assert len(bad) == 0, (path, run, mode, valid, ori, name, bad.tolist())
+            for name, (p, crun, want) in mc.CLAIMS.items():           # the named outcomes, read off the kernel's rows
+                if crun == run and (ori or p not in (mc.P_ROT1, mc.P_ROT2)):
+                    w = want(mode, valid)
+                    assert r.a2b[p, mc.PLANTED[name]] == (-1 if w is None else mc.KP[w]), (path, name, mode, valid, ori)
+            for p in mc.MALFORMED:
+                assert r.nmatches[p] == -1 and (r.b2a[p] == -1).all() and (r.a2b[p] == -1).all(), p
+    mb.close()
+
+
+def test_constructed_pairs_through_the_per_pair_entry_point(constructed):
+    """Frame mode: every well-formed pair equals orbx_search_by_bow (ORBmatcher.SearchByBoW) of the pair, which takes the hand-built
+    FeatureVectors as they are.  The two pairs with an empty FeatureVector on one side are left to the model: that entry point is not
+    given zero-length arrays here."""
+    c = constructed
+    ex = ORBextractor(*EUROC[2], device_id=0)
+    done = 0
+    for run, ratio in mc.RUNS.items():
+        for valid in (True, False):
+            for ori in (True, False):
+                m = ORBmatcher(ex, ratio, ori)
+                n, b2a, _ = c["want", run, FRAME, valid, ori]
+                for p, (ia, ib) in enumerate(mc.PAIRS.tolist()):
+                    if p in mc.MALFORMED or p in (mc.P_NOFV_A, mc.P_NOFV_B):
+                        continue
+                    (da, aa, va, fa), (db, ab, _, fb) = mc.frame(c, ia), mc.frame(c, ib)
+                    sn, sb2a = m.SearchByBoW(da, aa, va if valid else np.ones(len(da), np.uint8), fa, db, ab, fb)
+                    assert sn == n[p] and np.array_equal(sb2a, b2a[p, :len(db)]), (run, valid, ori, p)
+                    done += 1
+    assert done == len(mc.RUNS) * 4 * (len(mc.PAIRS) - len(mc.MALFORMED) - 2)

@@ -192,3 +192,189 @@ def test_a_stolen_acceptance_stays_in_the_histogram():
     assert run(f1, f2, window=10, ori=True, stats=st)[0] == [-1, 0, 1, 2, 3, -1, 5]
     assert st["steals"] == 1 and st["removed"] == 1
     assert run(f1, f2, window=10, ori=False)[0] == [-1, 0, 1, 2, 3, 4, 5]
+
+
+# ---- the constructed batch of tests/initmatch_cases.py, held to the oracle and to its own claims
+from tests import initmatch_cases as ic  # noqa: E402
+
+F32 = np.float32
+
+
+@functools.lru_cache(maxsize=None)
+def _case():
+    """The batch and -- computed once -- the model's (nmatches, matches12, prev) of every well-formed pair in every run, with and without
+    prev_xy, with and without check_orientation."""
+    c = ic.build()
+    want = {}
+    for run, (window, ratio, bounds) in ic.RUNS.items():
+        for p, (ia, ib) in enumerate(ic.PAIRS.tolist()):
+            if p in ic.MALFORMED:
+                continue
+            (k1, d1), (k2, d2) = ic.frame(c, ia), ic.frame(c, ib)
+            for ori in (True, False):
+                for given in (True, False):
+                    prev = c["prev"][p, :len(k1)] if given else None
+                    want[run, p, ori, given] = im.search_for_initialization(k1, d1, k2, d2, bounds, prev, window, ratio, ori)
+    return c, want
+
+
+@pytest.mark.parametrize("run", list(ic.RUNS))
+def test_the_model_is_the_oracle_on_the_constructed_batch(run):
+    c, want = _case()
+    window, ratio, bounds = ic.RUNS[run]
+    for p, (ia, ib) in enumerate(ic.PAIRS.tolist()):
+        if p in ic.MALFORMED:
+            continue
+        (k1, d1), (k2, d2) = ic.frame(c, ia), ic.frame(c, ib)
+        for ori in (True, False):
+            for given in (True, False):
+                p0 = c["prev"][p, :len(k1)] if given else np.stack([k1["x"], k1["y"]], 1).astype(np.float32).reshape(-1, 2)
+                on, om12, oprev = po.search_for_initialization(ic.reference_view(k1), d1, k2, d2, bounds, p0, window, ratio, ori)
+                n, m12, prev = want[run, p, ori, given]
+                assert n == on and np.array_equal(m12, om12), (run, p, ori, given)
+                assert (prev.tobytes() == oprev.tobytes()) if given else prev is None, (run, p, ori, given)
+
+
+def _held(want, name, ori=True):
+    """What the site's query holds after its run: (with prev_xy, without)."""
+    p, run, _, _ = ic.CLAIMS[name]
+    return tuple(int(want[run, p, ori, given][1][ic.PLANTED[name]]) for given in (True, False))
+
+
+def test_the_planted_sites_are_what_they_claim():
+    c, want = _case()
+    for name, (p, run, w_prev, w_none) in ic.CLAIMS.items():
+        expect = tuple(-1 if w is None else ic.KP[w] for w in (w_prev, w_none))
+        assert _held(want, name) == expect, (name, _held(want, name), expect)
+        if p not in (ic.P_ROTA, ic.P_ROTB):                       # every angle is 0: check_orientation changes nothing
+            assert _held(want, name, ori=False) == expect, name
+    # the rotation pairs without check_orientation: every site keeps what it was accepted with
+    for name, (p, run, _, _) in ic.CLAIMS.items():
+        if p in (ic.P_ROTA, ic.P_ROTB) and name != "rot_robbed":
+            assert _held(want, name, ori=False) == (ic.KP[name],) * 2, name
+    # a robbed query's prev row stays byte-identical; a matched one holds F2's position
+    for name in ("robbed", "chain_1", "chain_2", "equal_later", "ret_min_x", "ret_max_y"):
+        p, run, _, _ = ic.CLAIMS[name]
+        q = ic.PLANTED[name]
+        assert want[run, p, True, True][2][q].tobytes() == c["prev"][p, q].tobytes(), name
+    k2 = ic.frame(c, ic.PLANT2)[0]
+    for name in ("steals", "prev_moves", "ret_min_x_in"):
+        q, kp = ic.PLANTED[name], ic.KP[name]
+        assert want["main", ic.P_PLANT, True, True][2][q].tolist() == [k2["x"][kp], k2["y"][kp]], name
+    # the sites sit where they say: ties between two named features, steals counted by the model
+    assert ic.KP["tie_columns"] > ic.KP["tie_columns:higher_column"] and ic.KP["dup:later"] == ic.KP["dup"] + 64 - 2
+    for name in ("half_x", "half_y", "beyond_half_x", "beyond_half_y"):
+        assert ic.KP[name] == ic.KP[name + ":b"] > ic.KP[name + ":a"] and ic.KP[name + "_under"] == ic.KP[name + "_under:a"], name
+    st = {}
+    (k1, d1), (k2, d2) = ic.frame(c, ic.PLANT1), ic.frame(c, ic.PLANT2)
+    im.search_for_initialization(k1, d1, k2, d2, ic.B640, None, ic.WINDOW, ic.RATIO, False, stats=st)
+    assert st["steals"] == 3 and st["skipped_taken"] >= 2, st      # "steals" and the chain's two
+    st = {}
+    im.search_for_initialization(k1, d1, k2, d2, ic.B640, None, ic.WINDOW, 0.1, False, stats=st)
+    assert st["single_candidate"] >= 2
+    assert sorted(ic.MALFORMED.values()) == ["count above capacity", "frame", "negative count"]
+    assert c["counts"][ic.NEG, 0] < 0 and c["counts"][ic.OVER, 0] > ic.CAP and not 0 <= ic.PAIRS[ic.P_BADFRAME, 1] < ic.K
+    assert len(ic.PAIRS) <= 16 and c["kps"].shape == (ic.K, ic.CAP)
+
+
+def test_the_float32_facts_the_sites_rest_on():
+    c, _ = _case()
+    # the ratio product rounds to exactly `best` in float32 and lies above it: the float32 test fails, a double one would pass
+    best, second, ratio = ic.BEST, ic.SECOND, ic.RATIO
+    assert F32(second) * F32(ratio) == F32(best) and not F32(best) < F32(second) * F32(ratio)
+    assert float(best) < float(second) * float(F32(ratio)) and F32(best - 1) < F32(second) * F32(ratio) and best <= im.TH_LOW
+    assert F32(30) < F32(F32(im.INT_MAX) * F32(0.1)) and not F32(30) < F32(256) * F32(0.1)      # INT_MAX, not 256, is the lone candidate's second
+    # the tenth of thirty is three in float32, and above three once 0.1f is widened to double
+    assert F32(0.1) * F32(30) == F32(3.0) and float(F32(0.1)) * 30 > 3.0
+    assert im.three_maxima([30, 3, 2] + [0] * 27) == (0, 1, -1) and im.three_maxima([2, 0, 0, 2, 0, 0, 2, 0, 0, 2] + [0] * 20) == (0, 3, 6)
+    # the bin edges: the last rotation of bin 11, the first of bin 12, the fold, the negative differences
+    e11, e12 = ic.bin_edge(11)
+    assert np.nextafter(e11, F32(400)) == e12 and (im.rot_bin(e11, 0.0), im.rot_bin(e12, 0.0)) == (11, 12)
+    assert im.rot_bin(900.0, 0.0) == 0 and im._round(F32(F32(900.0) * (F32(1.0) / F32(30)))) == 30
+    assert im.rot_bin(0.0, 5.0) == 12 and im.rot_bin(10.0, 20.0) == 12 and F32(0.0) - F32(5.0) < 0
+    # the .5 grid positions under both bounds, in the specification's arithmetic
+    def pos(f, i, bounds):
+        k = c["kps"][f, i]
+        minx, miny, maxx, maxy = (F32(b) for b in bounds)
+        return float(F32(F32(k["x"]) - minx) * (F32(64) / F32(maxx - minx))), float(F32(F32(k["y"]) - miny) * (F32(48) / F32(maxy - miny)))
+    for name, axis in (("half_x", 0), ("half_y", 1)):
+        at, under = pos(ic.PLANT2, ic.KP[name + ":a"], ic.B640)[axis], pos(ic.PLANT2, ic.KP[name + "_under:a"], ic.B640)[axis]
+        assert at % 1 == 0.5 and under % 1 > 0.4999 and im._round(at) == int(at) + 1 and im._round(under) == int(under), (name, at, under)
+        k = ic.KP["beyond_" + name + ":cell"]
+        at = pos(ic.BEY2, ic.KP["beyond_" + name + ":a"], ic.BEYOND)[axis]
+        under = pos(ic.BEY2, ic.KP["beyond_" + name + "_under:a"], ic.BEYOND)[axis]
+        assert at == k + 0.5 and under % 1 < 0.5 and im._round(under) == int(under), (name, at, under)
+        assert im._round(pos(ic.BEY2, ic.KP["beyond_" + name + ":b"], ic.BEYOND)[axis]) == k
+    assert float(F32(64) / F32(ic.BEYOND[2] - ic.BEYOND[0])) != 64 / (ic.BEYOND[2] - ic.BEYOND[0])          # invW is not representable
+    for name, axis, at in (("neg_half_x", 0, -0.5), ("hi_half_x", 0, 63.5), ("neg_half_y", 1, -0.5), ("hi_half_y", 1, 47.5)):
+        assert pos(ic.PLANT2, ic.KP[name], ic.B640)[axis] == at, name
+        inside = pos(ic.PLANT2, ic.KP[name + "_in"], ic.B640)[axis]
+        assert abs(inside - at) < 1e-5 and 0 <= im._round(inside) < (64, 48)[axis] and not 0 <= im._round(at) < (64, 48)[axis], name
+    # the window's edge: exactly r away, and the last float32 below it
+    k1, k2 = c["kps"][ic.PLANT1], c["kps"][ic.PLANT2]
+    for name, f in (("win_at_x", "x"), ("win_at_y", "y")):
+        d_at = abs(F32(k2[f][ic.KP[name]]) - F32(k1[f][ic.PLANTED[name]]))
+        twin = name.replace("_at_", "_in_")
+        assert d_at == F32(ic.WINDOW) and np.nextafter(k2[f][ic.KP[twin]], F32(1e9)) == F32(k1[f][ic.PLANTED[twin]] + ic.WINDOW)
+        assert abs(F32(k2[f][ic.KP[twin]]) - F32(k1[f][ic.PLANTED[twin]])) < F32(ic.WINDOW)
+
+
+def _lengths(c, p, given=False):
+    """The candidate-list length of every query of pair p under run "main" (0: no level-0 query or nothing in the window)."""
+    ia, ib = ic.PAIRS[p]
+    (k1, _), (k2, _) = ic.frame(c, ia), ic.frame(c, ib)
+    keys, cstart, geo = im.build_grid(k2, ic.B640)
+    ctr = c["prev"][p] if given else np.stack([k1["x"], k1["y"]], 1)
+    return [len(im.window(ctr[i][0], ctr[i][1], ic.WINDOW, keys, cstart, geo, k2)) if k1["octave"][i] == 0 else 0 for i in range(len(k1))]
+
+
+def _chunks(lengths, room):
+    """The kernel's chunks of queries: each takes the longest run of queries whose lists fit the room together (one list always fits)."""
+    out, q0 = [], 0
+    while q0 < len(lengths):
+        q1, tot = q0 + 1, lengths[q0]
+        while q1 < len(lengths) and tot + lengths[q1] <= room:
+            tot += lengths[q1]
+            q1 += 1
+        out.append((q0, q1))
+        q0 = q1
+    return out
+
+
+def test_the_trips_chunks_and_sizes_of_the_batch():
+    c, want = _case()
+    # (j) three lane trips: 130 and more surviving candidates, the planted positions on the lanes they are meant for
+    for p, name in ((ic.P_LANE, "lane_pair"), (ic.P_TWIN, "lane_pair_twin")):
+        ia, ib = ic.PAIRS[p]
+        (k1, d1), (k2, d2) = ic.frame(c, ia), ic.frame(c, ib)
+        keys, cstart, geo = im.build_grid(k2, ic.B640)
+        lst = im.window(320.0, 240.0, ic.WINDOW, keys, cstart, geo, k2)
+        assert lst == list(range(130)), name                      # one cell: the list order is the index order
+        dist = [int(np.unpackbits(d1[0] ^ d2[i]).sum()) for i in lst]
+        assert dist[7] == 20 == min(dist) and dist[71] == sorted(dist)[1] == (22 if p == ic.P_LANE else 100) and 7 % 64 == 71 % 64
+        assert (F32(20) < F32(dist[71]) * F32(ic.RATIO)) == (p == ic.P_TWIN) and F32(20) < F32(sorted(dist)[2]) * F32(ic.RATIO)
+    lens = _lengths(c, ic.P_MANY)
+    q_rob, q_steal, q_dup = (ic.PLANTED[n] for n in ("group_robbed", "group_steals", "dup"))
+    assert (q_rob, q_steal, q_dup) == (63, 64, 65) and lens[:63] == [0] * 63 and lens[63:] == [132] * 3
+    (k1, d1), (k2, d2) = ic.frame(c, ic.MANYQ), ic.frame(c, ic.DENSE_A)
+    dist = [int(np.unpackbits(d1[q_dup] ^ d2[i]).sum()) for i in range(132)]
+    lo, hi = ic.KP["dup"], ic.KP["dup:later"]
+    assert dist[lo] == dist[hi] == min(dist) and [i for i, d in enumerate(dist) if d == min(dist)] == [lo, hi]
+    assert lo < 64 <= hi and hi % 64 < lo % 64                     # the later list position sits on the lower lane
+    assert 132 - 1 >= 130                                         # the stolen feature is skipped, 131 candidates survive
+    # (k) with room for one longest list the robbed query and the robber fall into different chunks; by default into different groups of 64
+    assert _chunks(lens, ic.CAP) == [(0, 64), (64, 65), (65, 66)] and max(lens) <= ic.CAP
+    assert q_rob // 64 != q_steal // 64
+    # (l) the sizes
+    for f, n0 in ic.N0.items():
+        keys, _, _ = im.build_grid(ic.frame(c, f)[0], ic.B640)
+        assert len(keys) == n0, (f, len(keys))
+    assert c["counts"][ic.NOLEVEL0, 0] > 0 and (ic.frame(c, ic.NOLEVEL0)[0]["octave"] != 0).all()
+    assert c["counts"][ic.EMPTY, 0] == 0 and c["counts"][ic.FULL, 0] == ic.CAP
+    assert [tuple(x) for x in ic.PAIRS[[ic.P_NOA, ic.P_NOB, ic.P_FULL]].tolist()] == [(ic.EMPTY, ic.PLANT2), (ic.PLANT1, ic.EMPTY), (ic.FULL, ic.FULL)]
+    for p in (ic.P_NOA, ic.P_NOB, ic.P_NOLEVEL0):                  # no acceptance at all, also under check_orientation
+        assert want["main", p, True, True][0] == 0
+    st = {}
+    k, d = ic.frame(c, ic.FULL)
+    n, _, _ = im.search_for_initialization(k, d, k, d, ic.B640, None, ic.WINDOW, ic.RATIO, True, stats=st)
+    assert n > 20 and st["skipped_taken"] > 0

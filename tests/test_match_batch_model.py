@@ -116,3 +116,112 @@ def test_taken_features_ties_and_the_rotation_filter():
     assert on == n and np.array_equal(ob2a, b2a)
     assert mm.rotation_bin(10.0, 25.0) == 12 and mm.rotation_bin(359.0, 0.0) == 12 and mm.rotation_bin(0.0, 1.0) == 12
     assert mm.rotation_bin(15.0, 0.0) == 1 and mm.rotation_bin(14.9, 0.0) == 0 and mm.rotation_bin(0.0, 346.0) == 0
+
+
+# ---- the constructed batch of tests/match_batch_cases.py, held to the oracle (frame mode) and to its own claims
+from tests import match_batch_cases as mc  # noqa: E402
+
+F32 = np.float32
+COMBOS = [(mode, valid, ori) for mode in (mm.FRAME, mm.KEYFRAMES) for valid in (True, False) for ori in (True, False)]
+
+
+@pytest.fixture(scope="module")
+def case():
+    """The batch and -- computed once -- the model's (nmatches, b2a) of every well-formed pair under every run, mode, valid form and
+    check_orientation."""
+    c = mc.build()
+    for run, ratio in mc.RUNS.items():
+        for mode, valid, ori in COMBOS:
+            for p, (ia, ib) in enumerate(mc.PAIRS.tolist()):
+                if p not in mc.MALFORMED:
+                    (da, aa, va, fa), (db, ab, vb, fb) = mc.frame(c, ia), mc.frame(c, ib)
+                    c["want", run, mode, valid, ori, p] = mm.search_by_bow(da, aa, va if valid else None, fa, db, ab, vb if valid else None, fb, mode, ratio, ori)
+    return c
+
+
+@pytest.mark.parametrize("run", list(mc.RUNS))
+def test_the_model_is_the_oracle_on_the_constructed_batch(case, run):
+    """Frame mode only: the oracle's SearchByBoW(KeyFrame, Frame) takes hand-built FeatureVectors, a keyframe-mode routine it has not."""
+    c = case
+    for p, (ia, ib) in enumerate(mc.PAIRS.tolist()):
+        if p in mc.MALFORMED:
+            continue
+        (da, aa, va, fa), (db, ab, _, fb) = mc.frame(c, ia), mc.frame(c, ib)
+        for valid in (True, False):
+            for ori in (True, False):
+                on, ob2a = po.search_by_bow(da, aa, va if valid else np.ones(len(da), np.uint8), fa, db, ab, fb, mc.RUNS[run], ori)
+                n, b2a = c["want", run, mm.FRAME, valid, ori, p]
+                assert n == on and np.array_equal(b2a, ob2a), (run, p, valid, ori)
+
+
+def test_the_planted_nodes_are_what_they_claim(case):
+    c = case
+    for name, (p, run, want) in mc.CLAIMS.items():
+        na = int(c["counts"][mc.PAIRS[p, 0], 0])
+        for mode, valid, ori in COMBOS:
+            if p in (mc.P_ROT1, mc.P_ROT2) and not ori:
+                expect = mc.KP[name]                              # without the filter every rotation site keeps its match
+            else:
+                w = want(mode, valid)
+                expect = -1 if w is None else mc.KP[w]
+            held = int(mm.invert(c["want", run, mode, valid, ori, p][1], na)[mc.PLANTED[name]])
+            assert held == expect, (name, mode, valid, ori, held, expect)
+    assert mc.KP["tie"] > mc.KP["tie:lower_index"]               # fv_feat order, not index order
+    fa = c["fv"][mc.MA]
+    assert any(l != sorted(l) for l in fa.values()) and any(l != sorted(l) for l in c["fv"][mc.MB].values())
+    assert mc.PLANTED["first_takes"] > mc.PLANTED["runner_up"]
+    assert c["valid"][mc.MA, mc.PLANTED["invalid_a"]] == 0 and c["valid"][mc.MB, mc.KP["invalid_b_best"]] == 0
+    # the node lists
+    nodes = lambda f: set(c["fv"][f])   # noqa: E731
+    assert not nodes(mc.E1) & nodes(mc.E2) and nodes(mc.E1) & nodes(mc.E3) == {min(nodes(mc.E1))} and nodes(mc.E1) & nodes(mc.E5) == {max(nodes(mc.E1))}
+    assert c["fv_n"][mc.NOFV] == 0 and nodes(mc.WA) - nodes(mc.WB1) and nodes(mc.MA) - nodes(mc.MB) and nodes(mc.MB) - nodes(mc.MA)
+    one_sided = min(nodes(mc.MA) - nodes(mc.MB))
+    assert min(nodes(mc.MA) & nodes(mc.MB)) < one_sided < max(nodes(mc.MA) & nodes(mc.MB))
+    # the malformed pairs, exactly as the header lists them
+    assert sorted(mc.MALFORMED.values()) == ["frame", "fv_feat entry at its frame's count", "negative count", "negative fv_n"]
+    assert c["counts"][mc.NEGCOUNT, 0] < 0 and c["fv_n"][mc.NEGFV] < 0 and not 0 <= mc.PAIRS[mc.P_BADFRAME, 1] < mc.K
+    f = mc.BADFEAT
+    assert (c["fv_feat"][f, :c["fv_ptr"][f, c["fv_n"][f]]] >= c["counts"][f, 0]).sum() == 1
+    # the arrays say what the dicts say
+    for f in range(mc.K):
+        k = max(int(c["fv_n"][f]), 0) if f != mc.NEGFV else len(c["fv"][f])
+        got = {int(c["fv_node"][f, j]): c["fv_feat"][f, c["fv_ptr"][f, j]:c["fv_ptr"][f, j + 1]].tolist() for j in range(k)}
+        if f != mc.BADFEAT:
+            assert got == c["fv"][f] and list(got) == sorted(got), f
+
+
+def test_the_float32_facts_the_nodes_rest_on():
+    best, second, ratio = mc.BEST, mc.SECOND, mc.RATIO
+    assert F32(ratio) * F32(second) == F32(best) and not F32(best) < F32(ratio) * F32(second) and best < 50
+    assert float(best) < float(F32(ratio)) * second and F32(best - 1) < F32(ratio) * F32(second)
+    assert F32(25) < F32(0.1) * F32(256) and not F32(26) < F32(0.1) * F32(256)          # 256, not INT_MAX, is a lone candidate's second
+    assert not F32(256) < F32(1.5) * F32(256) or 256 > 50
+    assert F32(0.1) * F32(30) == F32(3.0) and float(F32(0.1)) * 30 > 3.0
+    assert mm.three_maxima([30, 3, 2] + [0] * 27) == [0, 1, -1] and mm.three_maxima([2, 0, 0, 2, 0, 0, 2, 0, 0, 2] + [0] * 20) == [0, 3, 6]
+    e11, e12 = mc.bin_edge(11)
+    assert np.nextafter(e11, F32(400)) == e12 and (mm.rotation_bin(e11, 0.0), mm.rotation_bin(e12, 0.0)) == (11, 12)
+    assert mm.rotation_bin(900.0, 0.0) == 0 and mm.rotation_bin(0.0, 5.0) == 12 and mm.rotation_bin(10.0, 20.0) == 12
+
+
+def test_the_trips_of_the_batch(case):
+    """The list lengths and positions the wave-node sites rest on: 63 and 64 candidates stay in registers, 65 and 129 take two and three
+    trips; the twice-standing minimum's later position sits on the lower lane of a later trip."""
+    c = case
+    sizes = {name: len(c["fv"][f][n]) for name, f, n in (("nb_1", mc.WB1, 100), ("nb_63", mc.WB1, 163), ("nb_64", mc.WB1, 164), ("nb_65", mc.WB1, 165),
+                                                           ("nb_129", mc.WB2, 229), ("lane_pair", mc.WB2, 172), ("lane_pair_twin", mc.WB3, 173))}
+    assert sizes == mc.N_WAVE
+    for name, f, n in (("nb_63", mc.WB1, 163), ("nb_64", mc.WB1, 164), ("nb_65", mc.WB1, 165), ("nb_129", mc.WB2, 229)):
+        lst, (lo, hi) = c["fv"][f][n], mc.KP[name + ":positions"]
+        dist = [int(np.unpackbits(c["desc"][f, i]).sum()) for i in lst]           # the query is desc(0)
+        assert [j for j, d in enumerate(dist) if d == min(dist)] == [lo, hi] and lst[lo] == mc.KP[name] and lst[hi] == mc.KP[name + ":later"]
+        assert lst == sorted(lst, reverse=True)                   # positions run against the indices
+        if len(lst) > 64:
+            assert lo // 64 != hi // 64 and hi % 64 < lo % 64
+    for f, n, second in ((mc.WB2, 172, 22), (mc.WB3, 173, 100)):
+        dist = [int(np.unpackbits(c["desc"][f, i]).sum()) for i in c["fv"][f][n]]
+        assert dist[7] == 20 == min(dist) and dist[71] == second == sorted(dist)[1] and 7 % 64 == 71 % 64
+        assert (F32(20) < F32(mc.RATIO) * F32(second)) == (second == 100) and F32(20) < F32(mc.RATIO) * F32(sorted(dist)[2])
+    # the long chain: 70 A features over 4 candidates, four matches, and 66 A features find every candidate taken
+    assert len(c["fv"][mc.WA][300]) == 70 and len(c["fv"][mc.WB3][300]) == 4
+    n, b2a = c["want", "main", mm.FRAME, False, False, mc.P_W3]
+    assert sorted(b2a[c["fv"][mc.WB3][300]].tolist()) == sorted(c["fv"][mc.WA][300][:4]) and n == 5
