@@ -24,9 +24,12 @@
 
 #include "../orbx_internal.h"
 #include "../side/orbx_handle.h"
+#include "../side/orbx_pair_device.h"
 #include "../../../include/orbx_bow.h"
 
 namespace {
+
+using orbx::side::dev::block_scan;
 
 constexpr int kBowThreads = 512;     // k_bowb_frame: 8 waves
 constexpr int kBowLds = 4096;        // keys of one frame sorted in LDS: 32 KiB (a call uses 0 .. kBowLds, ORBX_BOW_LDS; larger frames sort in global memory)
@@ -63,22 +66,6 @@ __device__ __forceinline__ void bowb_sort(u64* K, int m) {
       __syncthreads();
     }
   }
-}
-
-// exclusive prefix of one int per thread over the workgroup; *total = the sum.  s_w: kBowThreads / 64 + 1 ints of LDS
-__device__ __forceinline__ int bowb_scan(int v, int* s_w, int* total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const int p = __shfl_up(inc, o); if (lane >= o) inc += p; }
-  __syncthreads();                       // s_w may still be read from the previous use
-  if (lane == 63) s_w[wv] = inc;
-  __syncthreads();
-  int base = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < kBowThreads / 64; w++) { const int t = s_w[w]; base += w < wv ? t : 0; all += t; }
-  *total = all;
-  return base + inc - v;
 }
 
 struct BowbArgs {
@@ -122,7 +109,7 @@ __device__ __forceinline__ void bowb_part(const BowbArgs& a, int f, int part, in
   int heads = 0;
   for (int j = j0; j < j1; j++) heads += j == 0 || (uint32_t)(K[j] >> 32) != (uint32_t)(K[j - 1] >> 32);
   int k = 0;
-  int out = bowb_scan(heads, s_w, &k);
+  int out = block_scan<kBowThreads / 64>(heads, s_w, &k);   // run heads before this thread's; k = all of them
   if (part == 1) {
     int32_t* ptr = a.fv_ptr + (size_t)f * (a.cap + 1);
     for (int j = j0; j < j1; j++) {

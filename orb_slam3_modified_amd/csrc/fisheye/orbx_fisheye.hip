@@ -94,22 +94,6 @@ __global__ __launch_bounds__(kFeQueries) void k_fe_knn(const uint8_t* __restrict
   }
 }
 
-// the exclusive prefix sum of v over the workgroup's 256 threads (4 waves), the total in *total
-__device__ __forceinline__ int fe_block_scan(int v, int* s_wave, int* total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const int p = __shfl_up(inc, o); if (lane >= o) inc += p; }
-  __syncthreads();                                                    // s_wave may still be read by the previous scan
-  if (lane == 63) s_wave[wv] = inc;
-  __syncthreads();
-  int before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < 4; w++) { const int s = s_wave[w]; all += s; before += w < wv ? s : 0; }
-  *total = all;
-  return before + inc - v;
-}
-
 __global__ __launch_bounds__(256) void k_fe_compact(const int32_t* __restrict__ countsL, const int32_t* __restrict__ countsR, int capL, int capR,
                                                     const int32_t* __restrict__ knn_idx, const unsigned long long* __restrict__ words,
                                                     orbx_fisheye_pair* __restrict__ pairs, int32_t* __restrict__ npairs) {
@@ -125,7 +109,7 @@ __global__ __launch_bounds__(256) void k_fe_compact(const int32_t* __restrict__ 
     for (int w0 = 0; w0 < nwords; w0 += 256) {
       const unsigned long long word = w0 + t < nwords ? words[(size_t)f * nwords + w0 + t] : 0ull;
       int total;
-      const int base = carry + fe_block_scan(__popcll(word), s_wave, &total);
+      const int base = carry + block_scan<4>(__popcll(word), s_wave, &total);
       s_base[t] = base; s_word[t] = word;
       __syncthreads();
       const int here = min(256, nwords - w0);

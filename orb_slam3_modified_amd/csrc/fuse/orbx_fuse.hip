@@ -40,7 +40,6 @@ static_assert(kCells == 3 * kGridThreads && (kCsStride * 4) % 16 == 0, "the scan
 
 constexpr size_t kX = offsetof(orbx_keypoint, x), kY = offsetof(orbx_keypoint, y), kOctave = offsetof(orbx_keypoint, octave);
 
-struct __align__(16) Rec { float x, y; int32_t octave; float ur; };
 struct __align__(16) Hdr {               // a keyframe's grid
   int32_t n, nin, omin, omax;            // count (-1: no grid), features in cells, their octaves' range
   float min_x, min_y, inv_w, inv_h;
@@ -320,16 +319,10 @@ int check_search(orbx_fuse* m, const char* who, const orbx_fuse_side* side, cons
 extern "C" {
 
 int orbx_fuse_create(orbx_fuse** out, int device) {
-  if (out) *out = nullptr;
-  if (!out) return create_fail(ORBX_E_INVALID, "orbx_fuse_create", "null argument");
-  if (device < 0) return create_fail(ORBX_E_INVALID, "orbx_fuse_create", "device must be >= 0");
-  orbx_fuse* m = new orbx_fuse();
-  m->lds_limit = env_int("ORBX_FUSE_LDS", 0, kLdsMax, kLdsMax);
-  const char* e = open_handle(m, device);
-  if (!e) e = allow_lds((const void*)k_fuse_search<true>, kLdsMax);
-  if (e) { orbx_fuse_destroy(m); return create_fail(ORBX_E_DEVICE, "orbx_fuse_create", e); }
-  *out = m;
-  return ORBX_OK;
+  return create_handle(out, device, "orbx_fuse_create", orbx_fuse_destroy, [](orbx_fuse* m) {
+    m->lds_limit = env_int("ORBX_FUSE_LDS", 0, kLdsMax, kLdsMax);
+    return allow_lds((const void*)k_fuse_search<true>, kLdsMax);
+  });
 }
 
 void orbx_fuse_destroy(orbx_fuse* m) {

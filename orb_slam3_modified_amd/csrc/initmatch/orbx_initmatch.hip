@@ -386,23 +386,13 @@ int check_call(orbx_initmatch* m, const char* who, const orbx_initmatch_side* a,
 extern "C" {
 
 int orbx_initmatch_create(orbx_initmatch** out, int device) {
-  if (out) *out = nullptr;
-  if (!out) return create_fail(ORBX_E_INVALID, "orbx_initmatch_create", "null argument");
-  if (device < 0) return create_fail(ORBX_E_INVALID, "orbx_initmatch_create", "device must be >= 0");
-  orbx_initmatch* m = new orbx_initmatch();
-  m->lds_limit = env_int("ORBX_INITMATCH_LDS", 0, kLdsMax, kLdsMax);
-  const char* e = open_handle(m, device);
-  if (!e) e = allow_lds((const void*)k_init_pairs<true>, kLdsMax);
-  if (e) { orbx_initmatch_destroy(m); return create_fail(ORBX_E_DEVICE, "orbx_initmatch_create", e); }
-  *out = m;
-  return ORBX_OK;
+  return create_handle(out, device, "orbx_initmatch_create", orbx_initmatch_destroy, [](orbx_initmatch* m) {
+    m->lds_limit = env_int("ORBX_INITMATCH_LDS", 0, kLdsMax, kLdsMax);
+    return allow_lds((const void*)k_init_pairs<true>, kLdsMax);
+  });
 }
 
-void orbx_initmatch_destroy(orbx_initmatch* m) {
-  if (!m) return;
-  close_handle(m);
-  delete m;
-}
+void orbx_initmatch_destroy(orbx_initmatch* m) { destroy_handle(m); }
 
 const char* orbx_initmatch_last_error(const orbx_initmatch* m) { return last_error(m); }
 
@@ -420,36 +410,22 @@ int orbx_initmatch_pairs_device(orbx_initmatch* m, const orbx_initmatch_side* a,
   const int capA = a->capacity, capB = b->capacity;
   int p2 = 2;
   while (p2 < capB) p2 <<= 1;
-  // the LDS path needs its arrays and room for one query's longest list (capB candidates); what is left of the limit is candidate room
-  const size_t fixed = layout(capA, capB, p2, true).fixed;
-  const size_t lds_limit = (size_t)m->lds_limit & ~(size_t)15;
-  const bool in_lds = fixed + 4 * (size_t)capB <= lds_limit;
+  Paths path;                              // one query's longest list is capB candidates
+  if ((rc = plan_paths(m, m->lds_limit, layout(capA, capB, p2, true).fixed, layout(capA, capB, p2, false).fixed, capB, npairs,
+                       {kMaxBlocks, kGlobalBlocks, kGlobalRoom}, &path)) != ORBX_OK) return rc;
   Args g;
   g.a = {(const uint8_t*)a->d_kps, a->d_desc, a->d_counts, a->nframes, capA};
   g.b = {(const uint8_t*)b->d_kps, b->d_desc, b->d_counts, b->nframes, capB};
   g.pairs = d_pairs; g.prev = d_prev_xy; g.m12 = d_matches12; g.m21 = d_matches21; g.nm = d_nmatches;
-  g.scratch = nullptr; g.scratch_stride = 0;
-  g.npairs = npairs; g.p2 = p2; g.check_ori = check_orientation != 0;
+  g.scratch = path.in_lds ? nullptr : m->scratch.p; g.scratch_stride = path.scratch_stride;
+  g.npairs = npairs; g.p2 = p2; g.room = path.room; g.check_ori = check_orientation != 0;
   g.minX = bounds[0]; g.minY = bounds[1];
   g.invW = (float)kCols / (bounds[2] - bounds[0]); g.invH = (float)kRows / (bounds[3] - bounds[1]);
   g.r = (float)window_size; g.ratio = nn_ratio;
-  size_t lds = 0;
-  int blocks;
-  if (in_lds) {
-    lds = lds_limit;
-    g.room = (int)((lds - fixed) / 4);
-    blocks = std::min(npairs, kMaxBlocks);
-  } else {
-    g.room = std::max(capB, kGlobalRoom);
-    blocks = std::min(npairs, kGlobalBlocks);
-    g.scratch_stride = (layout(capA, capB, p2, false).fixed + 4 * (size_t)g.room + 255) & ~(size_t)255;
-    if ((rc = grow(m, &m->scratch, g.scratch_stride * blocks)) != ORBX_OK) return rc;
-    g.scratch = m->scratch.p;
-  }
   hipStream_t st = stream ? (hipStream_t)stream : m->st;
   if ((rc = wait_previous(m, st)) != ORBX_OK) return rc;
-  if (in_lds) hipLaunchKernelGGL(k_init_pairs<true>, dim3((unsigned)blocks), dim3(kThreads), lds, st, g);
-  else hipLaunchKernelGGL(k_init_pairs<false>, dim3((unsigned)blocks), dim3(kThreads), 0, st, g);
+  if (path.in_lds) hipLaunchKernelGGL(k_init_pairs<true>, dim3((unsigned)path.blocks), dim3(kThreads), path.lds_bytes, st, g);
+  else hipLaunchKernelGGL(k_init_pairs<false>, dim3((unsigned)path.blocks), dim3(kThreads), 0, st, g);
   return record_call(m, st);
 }
 

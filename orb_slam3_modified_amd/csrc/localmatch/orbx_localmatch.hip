@@ -52,8 +52,6 @@ static_assert(kMaxCap == 32768, "15-bit indices and positions");
 
 constexpr size_t kX = offsetof(orbx_keypoint, x), kY = offsetof(orbx_keypoint, y), kOctave = offsetof(orbx_keypoint, octave);
 
-struct __align__(16) Rec { float x, y; int32_t octave; float ur; };
-
 // a / b for a normal a > 0 (64 and 48 here) and any b, rounded to nearest even as the float division is, by long division of the
 // significands in integers: the division's own expansion would put fused multiply-adds into the code object.  A zero or subnormal b gives an
 // infinity (64 / b is beyond FLT_MAX for every b below 1.9e-37), an infinite b a zero, a NaN itself.
@@ -433,23 +431,13 @@ int check_call(orbx_localmatch* m, const char* who, const orbx_localmatch_side* 
 extern "C" {
 
 int orbx_localmatch_create(orbx_localmatch** out, int device) {
-  if (out) *out = nullptr;
-  if (!out) return create_fail(ORBX_E_INVALID, "orbx_localmatch_create", "null argument");
-  if (device < 0) return create_fail(ORBX_E_INVALID, "orbx_localmatch_create", "device must be >= 0");
-  orbx_localmatch* m = new orbx_localmatch();
-  m->lds_limit = env_int("ORBX_LOCALMATCH_LDS", 0, kLdsMax, kLdsMax);
-  const char* e = open_handle(m, device);
-  if (!e) e = allow_lds((const void*)k_local_match<true>, kLdsMax);
-  if (e) { orbx_localmatch_destroy(m); return create_fail(ORBX_E_DEVICE, "orbx_localmatch_create", e); }
-  *out = m;
-  return ORBX_OK;
+  return create_handle(out, device, "orbx_localmatch_create", orbx_localmatch_destroy, [](orbx_localmatch* m) {
+    m->lds_limit = env_int("ORBX_LOCALMATCH_LDS", 0, kLdsMax, kLdsMax);
+    return allow_lds((const void*)k_local_match<true>, kLdsMax);
+  });
 }
 
-void orbx_localmatch_destroy(orbx_localmatch* m) {
-  if (!m) return;
-  close_handle(m);
-  delete m;
-}
+void orbx_localmatch_destroy(orbx_localmatch* m) { destroy_handle(m); }
 
 const char* orbx_localmatch_last_error(const orbx_localmatch* m) { return last_error(m); }
 
@@ -471,36 +459,22 @@ int orbx_localmatch_search_device(orbx_localmatch* m, const orbx_localmatch_side
   const int cap = side->capacity;
   int p2 = 2;
   while (p2 < cap) p2 <<= 1;
-  // the LDS path needs its arrays and room for one point's longest list (cap candidates); what is left of the limit is candidate room
-  const size_t fixed = layout(cap, mcap, p2, true).fixed;
-  const size_t lds_limit = (size_t)m->lds_limit & ~(size_t)15;
-  const bool in_lds = fixed + 4 * (size_t)cap <= lds_limit;
+  Paths path;                              // one point's longest list is cap candidates
+  if ((rc = plan_paths(m, m->lds_limit, layout(cap, mcap, p2, true).fixed, layout(cap, mcap, p2, false).fixed, cap, nitems,
+                       {kMaxBlocks, kGlobalBlocks, kGlobalRoom}, &path)) != ORBX_OK) return rc;
   Args g;
   g.kps = (const uint8_t*)side->d_kps; g.desc = side->d_desc; g.counts = side->d_counts; g.uright = side->d_uright; g.bounds = side->d_bounds;
   g.frames = d_frames; g.mp = d_mp; g.nmp = d_nmp; g.pdesc = d_pdesc;
   g.kp_obs = d_kp_obs; g.kp_match = d_kp_match; g.nmatches = d_nmatches;
-  g.scratch = nullptr; g.scratch_stride = 0;
-  g.nframes = side->nframes; g.cap = cap; g.nitems = nitems; g.mcap = mcap; g.npoints = npoints; g.nlevels = nlevels; g.p2 = p2;
+  g.scratch = path.in_lds ? nullptr : m->scratch.p; g.scratch_stride = path.scratch_stride;
+  g.nframes = side->nframes; g.cap = cap; g.nitems = nitems; g.mcap = mcap; g.npoints = npoints; g.nlevels = nlevels; g.p2 = p2; g.room = path.room;
   g.factor = (double)th != 1.0;            // bFactor, src/ORBmatcher.cc:48
   g.th = th; g.ratio = nn_ratio;
   for (int l = 0; l < ORBX_LOCALMATCH_MAX_LEVELS; l++) g.sf[l] = l < nlevels ? scale_factors[l] : 0.0f;
-  size_t lds = 0;
-  int blocks;
-  if (in_lds) {
-    lds = lds_limit;
-    g.room = (int)((lds - fixed) / 4);
-    blocks = std::min(nitems, kMaxBlocks);
-  } else {
-    g.room = std::max(cap, kGlobalRoom);
-    blocks = std::min(nitems, kGlobalBlocks);
-    g.scratch_stride = (layout(cap, mcap, p2, false).fixed + 4 * (size_t)g.room + 255) & ~(size_t)255;
-    if ((rc = grow(m, &m->scratch, g.scratch_stride * blocks)) != ORBX_OK) return rc;
-    g.scratch = m->scratch.p;
-  }
   hipStream_t st = stream ? (hipStream_t)stream : m->st;
   if ((rc = wait_previous(m, st)) != ORBX_OK) return rc;
-  if (in_lds) hipLaunchKernelGGL(k_local_match<true>, dim3((unsigned)blocks), dim3(kThreads), lds, st, g);
-  else hipLaunchKernelGGL(k_local_match<false>, dim3((unsigned)blocks), dim3(kThreads), 0, st, g);
+  if (path.in_lds) hipLaunchKernelGGL(k_local_match<true>, dim3((unsigned)path.blocks), dim3(kThreads), path.lds_bytes, st, g);
+  else hipLaunchKernelGGL(k_local_match<false>, dim3((unsigned)path.blocks), dim3(kThreads), 0, st, g);
   return record_call(m, st);
 }
 

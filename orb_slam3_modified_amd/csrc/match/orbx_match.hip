@@ -53,8 +53,6 @@ struct Args {
   float ratio;
 };
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
 constexpr size_t kAngle = offsetof(orbx_keypoint, angle);
 
 __device__ __forceinline__ void fail_rows(const Args& g, int p, int32_t* ob, int32_t* oa) {
@@ -160,9 +158,7 @@ __global__ __launch_bounds__(kThreads) void k_match_pairs(Args g) {
 
     // ---- one node per wave at a time
     for (;;) {
-      int w = 0;
-      if (lane == 0) w = atomicAdd(&s_next, 1);
-      w = __builtin_amdgcn_readfirstlane(w);
+      const int w = next_work(&s_next);
       if (w >= nwork) break;
       const int4 r = work[w];
       const int a0 = __builtin_amdgcn_readfirstlane(r.x), a1 = __builtin_amdgcn_readfirstlane(r.y);
@@ -315,24 +311,14 @@ int check_call(orbx_match* m, const char* who, const orbx_match_side* a, const o
 extern "C" {
 
 int orbx_match_create(orbx_match** out, int device) {
-  if (out) *out = nullptr;
-  if (!out) return create_fail(ORBX_E_INVALID, "orbx_match_create", "null argument");
-  if (device < 0) return create_fail(ORBX_E_INVALID, "orbx_match_create", "device must be >= 0");
-  orbx_match* m = new orbx_match();
-  m->lds_limit = env_int("ORBX_MATCH_LDS", 0, kLdsMax, kLdsMax);
-  m->wave_node = env_int("ORBX_MATCH_WAVE_NODE", 0, kWaveNode, kWaveNode);
-  const char* e = open_handle(m, device);
-  if (!e) e = allow_lds((const void*)k_match_pairs<true>, kLdsMax);
-  if (e) { orbx_match_destroy(m); return create_fail(ORBX_E_DEVICE, "orbx_match_create", e); }
-  *out = m;
-  return ORBX_OK;
+  return create_handle(out, device, "orbx_match_create", orbx_match_destroy, [](orbx_match* m) {
+    m->lds_limit = env_int("ORBX_MATCH_LDS", 0, kLdsMax, kLdsMax);
+    m->wave_node = env_int("ORBX_MATCH_WAVE_NODE", 0, kWaveNode, kWaveNode);
+    return allow_lds((const void*)k_match_pairs<true>, kLdsMax);
+  });
 }
 
-void orbx_match_destroy(orbx_match* m) {
-  if (!m) return;
-  close_handle(m);
-  delete m;
-}
+void orbx_match_destroy(orbx_match* m) { destroy_handle(m); }
 
 const char* orbx_match_last_error(const orbx_match* m) { return last_error(m); }
 

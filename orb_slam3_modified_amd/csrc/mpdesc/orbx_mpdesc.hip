@@ -267,25 +267,15 @@ int check_select(orbx_mpdesc* m, const char* who, const orbx_mpdesc_side* side, 
 extern "C" {
 
 int orbx_mpdesc_create(orbx_mpdesc** out, int device) {
-  if (out) *out = nullptr;
-  if (!out) return create_fail(ORBX_E_INVALID, "orbx_mpdesc_create", "null argument");
-  if (device < 0) return create_fail(ORBX_E_INVALID, "orbx_mpdesc_create", "device must be >= 0");
-  orbx_mpdesc* m = new orbx_mpdesc();
-  m->small_max = env_int("ORBX_MPDESC_SMALL_MAX", 0, kSmallCap, kSmallCap);
-  m->mid_max = env_int("ORBX_MPDESC_MID_MAX", 0, kMidCap, kMidCap);
-  const char* e = open_handle(m, device);
-  if (!e) e = allow_lds((const void*)k_mpd_point<true>, kMidLds);
-  if (!e) e = allow_lds((const void*)k_mpd_point<false>, kLargeLds);
-  if (e) { orbx_mpdesc_destroy(m); return create_fail(ORBX_E_DEVICE, "orbx_mpdesc_create", e); }
-  *out = m;
-  return ORBX_OK;
+  return create_handle(out, device, "orbx_mpdesc_create", orbx_mpdesc_destroy, [](orbx_mpdesc* m) {
+    m->small_max = env_int("ORBX_MPDESC_SMALL_MAX", 0, kSmallCap, kSmallCap);
+    m->mid_max = env_int("ORBX_MPDESC_MID_MAX", 0, kMidCap, kMidCap);
+    const char* e = allow_lds((const void*)k_mpd_point<true>, kMidLds);
+    return e ? e : allow_lds((const void*)k_mpd_point<false>, kLargeLds);
+  });
 }
 
-void orbx_mpdesc_destroy(orbx_mpdesc* m) {
-  if (!m) return;
-  close_handle(m);
-  delete m;
-}
+void orbx_mpdesc_destroy(orbx_mpdesc* m) { destroy_handle(m); }
 
 const char* orbx_mpdesc_last_error(const orbx_mpdesc* m) { return last_error(m); }
 

@@ -199,21 +199,13 @@ bool ascending(const int32_t* p, int n) {
 extern "C" {
 
 int orbx_score_create(orbx_score** out, int device) {
-  if (out) *out = nullptr;
-  if (!out) return create_fail(ORBX_E_INVALID, "orbx_score_create", "null argument");
-  if (device < 0) return create_fail(ORBX_E_INVALID, "orbx_score_create", "device must be >= 0");
-  orbx_score* s = new orbx_score();
-  s->lds_limit = env_int("ORBX_SCORE_LDS", 0, kScoreLds, kScoreLds);
-  if (const char* e = open_handle(s, device)) { orbx_score_destroy(s); return create_fail(ORBX_E_DEVICE, "orbx_score_create", e); }
-  *out = s;
-  return ORBX_OK;
+  return create_handle(out, device, "orbx_score_create", orbx_score_destroy, [](orbx_score* s) {
+    s->lds_limit = env_int("ORBX_SCORE_LDS", 0, kScoreLds, kScoreLds);
+    return (const char*)nullptr;
+  });
 }
 
-void orbx_score_destroy(orbx_score* s) {
-  if (!s) return;
-  close_handle(s);
-  delete s;
-}
+void orbx_score_destroy(orbx_score* s) { destroy_handle(s); }
 
 const char* orbx_score_last_error(const orbx_score* s) { return last_error(s); }
 

@@ -190,5 +190,43 @@ inline void close_handle(Handle* h) {
   if (h->st) (void)hipStreamDestroy(h->st);
 }
 
+// The create of a library whose handle is made from a device number alone: `who` is the entry point's name in the messages, init(handle)
+// reads the library's environment and raises its kernels' LDS limits (allow_lds) on the opened device: what failed, or nullptr.
+template <class H, class Init>
+int create_handle(H** out, int device, const char* who, void (*destroy)(H*), Init init) {
+  if (out) *out = nullptr;
+  if (!out) return create_fail(ORBX_E_INVALID, who, "null argument");
+  if (device < 0) return create_fail(ORBX_E_INVALID, who, "device must be >= 0");
+  H* h = new H();
+  const char* e = open_handle(h, device);
+  if (!e) e = init(h);
+  if (e) { destroy(h); return create_fail(ORBX_E_DEVICE, who, e); }
+  *out = h;
+  return ORBX_OK;
+}
+template <class H>
+void destroy_handle(H* h) {
+  if (!h) return;
+  close_handle(h);
+  delete h;
+}
+
+// Where a chunked window kernel keeps its arrays.  It needs `fixed_lds` bytes of arrays and room for one query's longest list (`longest`
+// candidates of 4 bytes); when that fits the handle's LDS limit, what is left of the limit is candidate room.  Otherwise every workgroup
+// gets a slice of the handle's scratch (grown here): `fixed_global` bytes and a room of at least global_room candidates.
+struct PathLimits { int lds_blocks, global_blocks, global_room; };
+struct Paths { bool in_lds; size_t lds_bytes; int room, blocks; size_t scratch_stride; };
+inline int plan_paths(Handle* h, int lds_limit, size_t fixed_lds, size_t fixed_global, int longest, int items, PathLimits lim, Paths* p) {
+  const size_t limit = (size_t)lds_limit & ~(size_t)15;
+  p->in_lds = fixed_lds + 4 * (size_t)longest <= limit;
+  if (p->in_lds) {
+    *p = {true, limit, (int)((limit - fixed_lds) / 4), std::min(items, lim.lds_blocks), 0};
+    return ORBX_OK;
+  }
+  const int room = std::max(longest, lim.global_room), blocks = std::min(items, lim.global_blocks);
+  *p = {false, 0, room, blocks, (fixed_global + 4 * (size_t)room + 255) & ~(size_t)255};
+  return grow(h, &h->scratch, p->scratch_stride * blocks);
+}
+
 }  // namespace side
 }  // namespace orbx

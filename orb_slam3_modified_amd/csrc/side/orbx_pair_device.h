@@ -1,5 +1,7 @@
 // The device helpers the batched pair matchers share (liborbx_match.so, liborbx_initmatch.so): descriptors and Hamming distances, the wave
-// minimum, the 32-bit top-2 keys (liborbx_fisheye.so), a chain's relaxed loads and stores, the rotation bin, the keypoint field reader and the LDS-DMA staging.  Device code only; it
+// minimum, the 32-bit top-2 keys (liborbx_fisheye.so), a chain's relaxed loads and stores, the rotation bin, the keypoint field reader, the LDS-DMA staging,
+// the frame grid's record (liborbx_fuse.so, liborbx_localmatch.so), a work list's pop (liborbx_trimatch.so) and the workgroup scan
+// (liborbx_bow.so, liborbx_fisheye.so).  Device code only; it
 // sits below csrc/, outside kernels_hash().  A kernel's file imports the names with `using namespace orbx::side::dev;` inside its anonymous
 // namespace.  ComputeThreeMaxima and the trip loop's three-reduction merge stay written out in both kernels: as functions of this header
 // they change the kernels' instruction streams (the compiler unrolls and schedules them differently).
@@ -15,6 +17,9 @@ namespace side {
 namespace dev {
 
 struct D8 { uint32_t w[8]; };
+
+// a sorted position's record in a frame grid (liborbx_fuse.so, liborbx_localmatch.so): what a window test reads of its keypoint
+struct __align__(16) Rec { float x, y; int32_t octave; float ur; };
 
 __device__ __forceinline__ D8 load_desc(const uint8_t* p) {
   const uint4 x = ((const uint4*)p)[0], y = ((const uint4*)p)[1];
@@ -84,6 +89,33 @@ __device__ __forceinline__ void stage_dma(uint8_t* dst, const uint8_t* src, int 
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (size_t)i * 16),
                                        (__attribute__((address_space(3))) void*)d, 16, 0, 0);
   }
+}
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+
+// the wave's next item of a work list: lane 0 takes it from the LDS counter, wave-uniform
+__device__ __forceinline__ int next_work(int* s_next) {
+  int w = 0;
+  if ((threadIdx.x & 63) == 0) w = atomicAdd(s_next, 1);
+  return __builtin_amdgcn_readfirstlane(w);
+}
+
+// the exclusive prefix sum of v over the workgroup's WAVES waves, the sum in *total: a shuffle scan inside the wave, the wave sums through
+// s_wave[WAVES], which may still be read from the previous use
+template <int WAVES>
+__device__ __forceinline__ int block_scan(int v, int* s_wave, int* total) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  int inc = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) { const int p = __shfl_up(inc, o); if (lane >= o) inc += p; }
+  __syncthreads();
+  if (lane == 63) s_wave[wv] = inc;
+  __syncthreads();
+  int before = 0, all = 0;
+#pragma unroll
+  for (int w = 0; w < WAVES; w++) { const int s = s_wave[w]; before += w < wv ? s : 0; all += s; }
+  *total = all;
+  return before + inc - v;
 }
 
 }  // namespace dev

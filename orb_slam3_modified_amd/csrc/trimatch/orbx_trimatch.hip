@@ -60,8 +60,6 @@ struct Args {
 
 __host__ __device__ inline int max_work(int capA, int capB) { return (capA < capB ? capA : capB) + capA / kChunk + 1; }
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
 constexpr size_t kX = offsetof(orbx_keypoint, x), kY = offsetof(orbx_keypoint, y), kAngle = offsetof(orbx_keypoint, angle),
                  kOctave = offsetof(orbx_keypoint, octave);
 
@@ -218,9 +216,7 @@ __global__ __launch_bounds__(kThreads) void k_tri_pairs(Args g) {
 
     // ---- one chunk of queries per wave at a time
     for (;;) {
-      int w = 0;
-      if (lane == 0) w = atomicAdd(&s_next, 1);
-      w = __builtin_amdgcn_readfirstlane(w);
+      const int w = next_work(&s_next);
       if (w >= nwork) break;
       const int4 r = work[w];
       const int a0 = __builtin_amdgcn_readfirstlane(r.x), a1 = __builtin_amdgcn_readfirstlane(r.y);
@@ -354,23 +350,13 @@ int check_call(orbx_trimatch* m, const char* who, const orbx_trimatch_side* a, c
 extern "C" {
 
 int orbx_trimatch_create(orbx_trimatch** out, int device) {
-  if (out) *out = nullptr;
-  if (!out) return create_fail(ORBX_E_INVALID, "orbx_trimatch_create", "null argument");
-  if (device < 0) return create_fail(ORBX_E_INVALID, "orbx_trimatch_create", "device must be >= 0");
-  orbx_trimatch* m = new orbx_trimatch();
-  m->lds_limit = env_int("ORBX_TRIMATCH_LDS", 0, kLdsMax, kLdsMax);
-  const char* e = open_handle(m, device);
-  if (!e) e = allow_lds((const void*)k_tri_pairs<true>, kLdsMax);
-  if (e) { orbx_trimatch_destroy(m); return create_fail(ORBX_E_DEVICE, "orbx_trimatch_create", e); }
-  *out = m;
-  return ORBX_OK;
+  return create_handle(out, device, "orbx_trimatch_create", orbx_trimatch_destroy, [](orbx_trimatch* m) {
+    m->lds_limit = env_int("ORBX_TRIMATCH_LDS", 0, kLdsMax, kLdsMax);
+    return allow_lds((const void*)k_tri_pairs<true>, kLdsMax);
+  });
 }
 
-void orbx_trimatch_destroy(orbx_trimatch* m) {
-  if (!m) return;
-  close_handle(m);
-  delete m;
-}
+void orbx_trimatch_destroy(orbx_trimatch* m) { destroy_handle(m); }
 
 const char* orbx_trimatch_last_error(const orbx_trimatch* m) { return last_error(m); }
 

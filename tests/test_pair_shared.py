@@ -17,6 +17,26 @@ def test_device_helpers_are_defined_once_in_the_shared_header():
         assert where == [os.path.join("side", "orbx_pair_device.h")], (name, where)
 
 
+SIDE_LIBS = ("side", "match", "initmatch", "trimatch", "fuse", "localmatch", "bow", "fisheye", "mpdesc", "score")
+
+
+def test_helpers_shared_since_are_defined_once_in_side():
+    src = _sources(*SIDE_LIBS)
+    for name, home in (("clampi", "orbx_pair_device.h"), ("next_work", "orbx_pair_device.h"), ("block_scan", "orbx_pair_device.h"),
+                       ("create_handle", "orbx_handle.h"), ("destroy_handle", "orbx_handle.h"), ("plan_paths", "orbx_handle.h")):
+        where = [f for f, text in src.items() for _ in re.finditer(r"^[^\n;=]*\b(?:int|void)\s+%s\s*\([^;{]*\)\s*\{" % name, text, flags=re.M)]
+        assert where == [os.path.join("side", home)], (name, where)
+    for gone in ("bowb_scan", "fe_block_scan"):
+        assert not [f for f, text in src.items() if gone in text], gone
+    assert [f for f, text in src.items() if re.search(r"\bstruct\s+(?:__align__\(16\)\s+)?Rec\b", text)] == [os.path.join("side", "orbx_pair_device.h")]
+
+
+def test_the_create_triads_go_through_the_helper():
+    for d in ("match", "initmatch", "trimatch", "fuse", "localmatch", "mpdesc", "score"):
+        for f, text in _sources(d).items():
+            assert "create_handle(out, device," in text and "new orbx_" not in text, f
+
+
 def test_host_pieces_are_not_redefined():
     for f, text in _sources("match", "initmatch", "bow").items():
         for gone in ("struct Layout", "struct HostLayout", "a buffer lives on device"):
