@@ -10,7 +10,7 @@
  * Out of scope:
  *   the two-camera block (:143-210);
  *   the projection that produces those members (Frame::isInFrustum): the caller's Eigen and libm work;
- *   SearchByProjection(Frame, LastFrame) (:1676): the frame-to-last-frame form stays with orbx_search_by_projection_last.
+ *   SearchByProjection(Frame, LastFrame) (:1676): the frame-to-last-frame form is include/orbx_lastmatch.h's (liborbx_lastmatch.so).
  *
  * The specification is the reference's loop.  For item b, frame f = frames[b], the item's map points in index order:
  *   1. a point with in_view == 0 is skipped.  The caller folds !mbTrackInView, isBad() and the far-point test into the flag, as

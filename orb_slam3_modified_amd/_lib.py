@@ -24,6 +24,7 @@ MPDESC_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_mpdesc.so")  
 SCORE_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_score.so")           # the six DBoW2 scorings (include/orbx_score.h)
 FISHEYE_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_fisheye.so")       # the batched two-camera rig front-end (include/orbx_fisheye.h)
 LOCALMATCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_localmatch.so")   # the batched SearchLocalPoints (include/orbx_localmatch.h)
+LASTMATCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_lastmatch.so")     # the batched SearchByProjection(Frame, LastFrame) (include/orbx_lastmatch.h)
 
 ORBX_OK, ORBX_E_INVALID, ORBX_E_EMPTY, ORBX_E_DEVICE, ORBX_E_CAPACITY, ORBX_E_FORMAT = 0, -1, -2, -3, -4, -5
 NUM_KERNELS = 6
@@ -431,9 +432,31 @@ def localmatch_lib(path: str = LOCALMATCH_LIB_PATH) -> C.CDLL:
     return M
 
 
+class OrbxLastMatchSide(C.Structure):
+    """orbx_lastmatch_side (include/orbx_lastmatch.h)."""
+    _fields_ = [("d_kps", C.c_void_p), ("d_desc", C.c_void_p), ("d_counts", C.c_void_p), ("d_uright", C.c_void_p), ("d_bounds", C.c_void_p),
+                ("nframes", C.c_int), ("capacity", C.c_int)]
+
+
+def lastmatch_lib(path: str = LASTMATCH_LIB_PATH) -> C.CDLL:
+    """liborbx_lastmatch.so.  `_orbx_lastmatch_symbols`: every name of include/orbx_lastmatch.h, bound here with its signature.  `path`: a
+    timing build of the same source (tools/lastmatch_times.py)."""
+    vp, i32, sp, fp = C.c_void_p, C.c_int, C.POINTER(OrbxLastMatchSide), C.POINTER(C.c_float)
+    sig = {
+        "orbx_lastmatch_create": (i32, [C.POINTER(vp), i32]),
+        "orbx_lastmatch_destroy": (None, [vp]),
+        "orbx_lastmatch_last_error": (C.c_char_p, [vp]),
+        "orbx_lastmatch_search_device": (i32, [vp, sp, vp, i32, vp, vp, i32, vp, i32, fp, i32, i32, vp, vp, vp, vp]),
+        "orbx_lastmatch_search": (i32, [vp, sp, vp, i32, vp, vp, i32, vp, i32, fp, i32, i32, vp, vp, vp]),
+    }
+    M = _load_side(path, sig)
+    M._orbx_lastmatch_symbols = tuple(sig)
+    return M
+
+
 class SideHandle:
     """A handle of a side library whose entry points are <prefix>_create / _destroy / _last_error (StereoBatch, BowBatch, MatchBatch,
-    InitMatchBatch, TriMatchBatch, FuseBatch, DistinctBatch, ScoreBatch, FisheyeBatch, LocalMatchBatch)."""
+    InitMatchBatch, TriMatchBatch, FuseBatch, DistinctBatch, ScoreBatch, FisheyeBatch, LocalMatchBatch, LastMatchBatch)."""
 
     def __init__(self, library: C.CDLL, prefix: str, *create_args):
         self._L, self._prefix, self._h = library, prefix, C.c_void_p(0)

@@ -1,0 +1,133 @@
+"""The batched frame-to-last-frame matcher over liborbx_lastmatch.so (include/orbx_lastmatch.h): ORBmatcher::SearchByProjection(CurrentFrame,
+LastFrame, th, bMono) (src/ORBmatcher.cc:1676-1885, Nleft == -1) for B (current frame, last frame's points) items at once on the keypoints
+and descriptors a batch extraction left in HBM and the descriptor pool DistinctBatch fills.  All matching arithmetic runs in the HIP kernel
+of the library; this file only marshals buffers.  The caller projects the last frame's points (:1686-1718, bForward / bBackward included)
+and applies kp_match to its mvpMapPoints."""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+
+from . import _lib
+from ._lib import KP_DTYPE, OrbxLastMatchSide, addr, host_array as arr, host_view, ptr
+
+LDS_MAX = 148 * 1024     # the largest dynamic LDS block of a workgroup (ORBX_LASTMATCH_LDS lowers it)
+MAX_CAPACITY = 32768
+MAX_LEVELS = 16
+ITEM_DTYPE = np.dtype([("frame", "<i4"), ("direction", "<i4"), ("mbf", "<f4"), ("th", "<f4")])
+POINT_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("invz", "<f4"), ("angle", "<f4"), ("octave", "<i4"), ("obs", "<i4"), ("point", "<i4"),
+                        ("valid", "<i4")])
+assert ITEM_DTYPE.itemsize == 16 and POINT_DTYPE.itemsize == 32
+
+
+def _up16(n: int) -> int:
+    return (n + 15) & ~15
+
+
+def lds_bytes(capacity: int, mcap: int) -> int:
+    """What the LDS path needs beside the candidate room for frames of this capacity and rows of up to `mcap` points: descriptors, sorted
+    keys, records, cell starts, offsets, the points' results.  A search takes the LDS path when this plus one list of `capacity` candidates
+    is within the handle's limit; the rest of the limit is candidate room (4 bytes a candidate)."""
+    p2 = 2
+    while p2 < capacity:
+        p2 <<= 1
+    return sum(_up16(b) for b in (32 * capacity, 4 * p2, 16 * capacity, 2 * (64 * 48 + 1), 4 * (mcap + 1), 4 * mcap))
+
+
+@dataclass
+class LastMatchSide:
+    """The frame side (orbx_lastmatch_side): kps [F, cap] keypoints (28 bytes each), desc [F, cap, 32], counts [F, 2], bounds [F, 4]
+    float32 = {min_x, min_y, max_x, max_y}, uright [F, cap] float32 or None (monocular).  Torch tensors or raw HBM addresses for
+    search_device, numpy arrays for search."""
+    kps: object
+    desc: object
+    counts: object
+    bounds: object
+    nframes: int
+    capacity: int
+    uright: object = None
+
+    def _struct(self) -> OrbxLastMatchSide:
+        return OrbxLastMatchSide(*(addr(t) or None for t in (self.kps, self.desc, self.counts, self.uright, self.bounds)), int(self.nframes),
+                                 int(self.capacity))
+
+    def _host(self) -> "LastMatchSide":
+        """Contiguous numpy arrays of the ABI's element types."""
+        K, cap = int(self.nframes), int(self.capacity)
+        kps = np.ascontiguousarray(self.kps)
+        assert kps.nbytes == K * cap * KP_DTYPE.itemsize
+        return LastMatchSide(kps, arr(self.desc, np.uint8, K, cap, 32), arr(self.counts, np.int32, K, 2), arr(self.bounds, np.float32, K, 4), K,
+                             cap, None if self.uright is None else arr(self.uright, np.float32, K, cap))
+
+
+@dataclass
+class LastMatchResult:
+    """nmatches [B] (-1 for a malformed item), kp_match [B, cap] (the item's point bound to each keypoint, -1 untouched, -2 set to NULL by
+    the rotation filter) and kp_obs [B, cap] (the rows after the call); torch tensors from search_device, numpy arrays from search.
+    result[b] = (nmatches, kp_match row, kp_obs row) of item b on the host."""
+    nmatches: object
+    kp_match: object
+    kp_obs: object
+
+    def __len__(self) -> int:
+        return int(self.nmatches.shape[0])
+
+    def __getitem__(self, b: int):
+        return int(host_view(self.nmatches[b:b + 1])[0]), host_view(self.kp_match[b]), host_view(self.kp_obs[b])
+
+
+def _table(scale_factors):
+    s = np.ascontiguousarray(scale_factors, np.float32).ravel()
+    return s, s.ctypes.data_as(C.POINTER(C.c_float)), len(s)
+
+
+class LastMatchBatch(_lib.SideHandle):
+    """TrackWithMotionModel's matcher for batches of (current frame, last frame's points) items; one handle holds one stream and its
+    scratch on one GPU."""
+
+    def __init__(self, device_id: int = 0, library_path: Optional[str] = None):
+        self._M = _lib.lastmatch_lib(library_path) if library_path else _lib.lastmatch_lib()
+        self.device_id = int(device_id)
+        super().__init__(self._M, "orbx_lastmatch", int(device_id))
+
+    def search_device(self, side: LastMatchSide, items, points, nlast, pdesc, scale_factors, kp_obs, check_orientation: bool = True, stream=None,
+                      out: Optional[LastMatchResult] = None, nitems: Optional[int] = None, mcap: Optional[int] = None,
+                      npoints: Optional[int] = None) -> LastMatchResult:
+        """orbx_lastmatch_search_device: `items` [B] records of ITEM_DTYPE (a [B, 16] uint8 tensor), `points` [B, mcap] records of
+        POINT_DTYPE (a [B, mcap, 32] uint8 tensor), `nlast` [B] int32, `pdesc` [M, 32] uint8 and `kp_obs` [B, cap] int32 (updated in place)
+        on the device, `scale_factors` a host array; asynchronous on `stream` (None or 0: the handle's own).  Without `out` kp_match and
+        nmatches are allocated on the items' device (torch); the result's kp_obs is the tensor passed in."""
+        B = int(items.shape[0]) if nitems is None else int(nitems)
+        Q = int(points.shape[1]) if mcap is None else int(mcap)
+        M = int(pdesc.shape[0]) if npoints is None else int(npoints)
+        if out is None:
+            import torch
+            dev = items.device if hasattr(items, "device") else torch.device("cuda", self.device_id)
+            out = LastMatchResult(torch.empty(B, dtype=torch.int32, device=dev),
+                                  torch.empty((B, int(side.capacity)), dtype=torch.int32, device=dev), kp_obs)
+        s = side._struct()
+        _keep, pt, nl = _table(scale_factors)
+        self._check(self._M.orbx_lastmatch_search_device(self._h, C.byref(s), ptr(addr(items)), B, ptr(addr(points)), ptr(addr(nlast)), Q,
+                                                         ptr(addr(pdesc)), M, pt, nl, int(bool(check_orientation)), ptr(addr(kp_obs)),
+                                                         ptr(addr(out.kp_match)), ptr(addr(out.nmatches)), ptr(int(stream or 0))))
+        return out
+
+    def search(self, side: LastMatchSide, items, points, nlast, pdesc, scale_factors, kp_obs, check_orientation: bool = True) -> LastMatchResult:
+        """orbx_lastmatch_search on numpy arrays of the same layout (`items` [B] of ITEM_DTYPE, `points` [B, mcap] of POINT_DTYPE); returns
+        when the results are on the host.  `kp_obs` is not changed: the updated rows are the result's."""
+        hs = side._host()
+        points = np.ascontiguousarray(points, POINT_DTYPE)
+        B, Q = points.shape
+        items = np.ascontiguousarray(items, ITEM_DTYPE).reshape(B)
+        nlast = arr(nlast, np.int32, B)
+        pdesc = np.ascontiguousarray(pdesc, np.uint8).reshape(-1, 32)
+        obs = arr(kp_obs, np.int32, B, hs.capacity).copy()
+        out = LastMatchResult(np.zeros(B, np.int32), np.zeros((B, hs.capacity), np.int32), obs)
+        s = hs._struct()
+        _keep, pt, nl = _table(scale_factors)
+        self._check(self._M.orbx_lastmatch_search(self._h, C.byref(s), ptr(items), B, ptr(points), ptr(nlast), Q, ptr(pdesc), len(pdesc), pt, nl,
+                                                  int(bool(check_orientation)), ptr(obs), ptr(out.kp_match), ptr(out.nmatches)))
+        return out

@@ -1,0 +1,143 @@
+"""include/orbx_lastmatch.h <-> liborbx_lastmatch.so: the batched frame-to-last-frame matcher is a library of its own beside the product
+(CPU-only checks)."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+from tests import abi_util
+from tests.abi_util import declared as _declared, exported as _exported
+
+ROOT = abi_util.ROOT
+KERNELS_HASH = "cfa5f580d25d496f"   # the product's kernel sources: this library changes none of them
+HEADER = "orbx_lastmatch.h"
+NAMES = ("create", "destroy", "last_error", "search_device", "search")
+FUSED_F32 = r"v_(pk_)?(fma|fmac|fmaak|fmamk|mad|madak|madmk)_f32"
+
+
+def test_build_produces_the_lastmatch_library():
+    from orb_slam3_modified_amd import _lib, build
+    build.build()
+    assert os.path.isfile(build.LASTMATCH_OUT) and build.LASTMATCH_OUT == _lib.LASTMATCH_LIB_PATH
+    assert os.path.dirname(build.LASTMATCH_OUT) == os.path.dirname(_lib.LIB_PATH) == os.path.join(ROOT, "orb_slam3_modified_amd")
+    assert os.path.basename(build.LASTMATCH_OUT) == "liborbx_lastmatch.so"
+    assert HEADER in build.HEADERS
+    rec = [l for l in build.LIBS if l.out == build.LASTMATCH_OUT]
+    assert len(rec) == 1 and rec[0].sources == (build.LASTMATCH_SOURCE,) and rec[0].hidden
+    assert "-ffp-contract=off" in build.FLAGS       # the radius', the gate's and the grid's float expressions are not contracted
+
+
+def test_lastmatch_library_exports_exactly_its_header():
+    from orb_slam3_modified_amd import _lib, build
+    build.build()
+    names = _declared(HEADER)
+    assert names == sorted("orbx_lastmatch_" + n for n in NAMES), names
+    exported = _exported(_lib.LASTMATCH_LIB_PATH)
+    assert {e for e in exported if e.startswith("orbx_")} == set(names)
+    assert not [e for e in exported if not e.startswith("orbx_lastmatch_") and not e.startswith("_")], sorted(exported)[:10]   # -fvisibility=hidden
+
+
+def test_product_library_keeps_its_abi_and_its_kernels():
+    from orb_slam3_modified_amd import _lib, build
+    build.build()
+    names = set(_declared(HEADER))
+    for other in (_lib.LIB_PATH, _lib.FUSE_LIB_PATH, _lib.INITMATCH_LIB_PATH, _lib.MPDESC_LIB_PATH, _lib.MATCH_LIB_PATH, _lib.TRIMATCH_LIB_PATH,
+                  _lib.LOCALMATCH_LIB_PATH):
+        assert not names & _exported(other), other
+    assert not names & set(_declared("orbx.h"))
+    assert len(_declared("orbx.h")) == 100
+    assert build.kernels_hash() == KERNELS_HASH
+    assert os.path.dirname(build.LASTMATCH_SOURCE) == "lastmatch" and "orbx_lastmatch.hip" not in os.listdir(build.CSRC)
+    src = open(os.path.join(build.CSRC, build.LASTMATCH_SOURCE)).read()
+    assert "side/orbx_handle.h" in src and "side/orbx_pair_device.h" in src and "orbx_internal.h" not in src
+
+
+@pytest.mark.skipif(shutil.which("gcc") is None, reason="gcc not installed")
+def test_the_header_compiles_as_c(tmp_path):
+    src = tmp_path / "use.c"
+    src.write_text('#include "orbx_lastmatch.h"\nint main(void) { orbx_lastmatch_point q; orbx_lastmatch_side s; orbx_lastmatch_item i; '
+                   'return (int)sizeof(q) - 32 + (int)sizeof(s) - 48 + (int)sizeof(i) - 16; }\n')
+    exe = tmp_path / "use.o"
+    p = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), "-c", str(src), "-o", str(exe)],
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert p.returncode == 0, p.stdout[-2000:]
+
+
+def test_python_binding_covers_the_header():
+    from orb_slam3_modified_amd import _lib, build
+    build.build()
+    M = _lib.lastmatch_lib()
+    assert set(M._orbx_lastmatch_symbols) == set(_declared(HEADER))
+    from orb_slam3_modified_amd import lastmatch, localmatch
+    assert issubclass(lastmatch.LastMatchBatch, _lib.SideHandle)
+    for m in ("search_device", "search"):
+        assert callable(getattr(lastmatch.LastMatchBatch, m))
+    # the structures the binding passes are the header's: the same fields, in order and size
+    in_header = abi_util.struct_fields(HEADER, "orbx_lastmatch_side")
+    assert in_header == [f for f, _ in _lib.OrbxLastMatchSide._fields_] == abi_util.struct_fields("orbx_localmatch.h", "orbx_localmatch_side")
+    assert C.sizeof(_lib.OrbxLastMatchSide) == 5 * 8 + 2 * 4
+    assert abi_util.struct_fields(HEADER, "orbx_lastmatch_point") == list(lastmatch.POINT_DTYPE.names) and lastmatch.POINT_DTYPE.itemsize == 32
+    assert abi_util.struct_fields(HEADER, "orbx_lastmatch_item") == list(lastmatch.ITEM_DTYPE.names) and lastmatch.ITEM_DTYPE.itemsize == 16
+    # the sizing formula the binding states is the library's (the layout is localmatch's): EuRoC's capacity with 1024 points fits the LDS
+    # with room for more than 16 000 candidates, the initialisation extractor's capacity does not fit
+    assert lastmatch.lds_bytes(1024, 1024) + 4 * 16000 <= lastmatch.LDS_MAX < lastmatch.lds_bytes(5024, 1024)
+    assert lastmatch.lds_bytes(1024, 2048) == localmatch.lds_bytes(1024, 2048)
+    src = open(os.path.join(build.CSRC, build.LASTMATCH_SOURCE)).read()
+    assert "kLdsMax = 148 * 1024" in src and '"ORBX_LASTMATCH_LDS"' in src
+    # the header states what is out of scope and what is undefined
+    text = open(os.path.join(ROOT, "include", HEADER)).read()
+    for word in ("two-camera block", "bForward", "non-finite", "asserts", "mo_search_by_projection_last", "ORBX_LASTMATCH_LDS", "ComputeThreeMaxima"):
+        assert word in text, word
+    assert "orbx_lastmatch.h" in open(os.path.join(ROOT, "include", "orbx_localmatch.h")).read()
+
+
+def test_bad_arguments_are_rejected_without_a_device():
+    """Argument checks that come before any device call, both forms."""
+    from orb_slam3_modified_amd import _lib
+    M = _lib.lastmatch_lib()
+    h = C.c_void_p(0)
+    assert M.orbx_lastmatch_create(None, 0) == _lib.ORBX_E_INVALID
+    assert b"null" in M.orbx_lastmatch_last_error(None)
+    assert M.orbx_lastmatch_create(C.byref(h), -1) == _lib.ORBX_E_INVALID and not h.value
+    assert b"device" in M.orbx_lastmatch_last_error(None)
+    side = _lib.OrbxLastMatchSide()
+    tab = (C.c_float * 16)(*([1.0] * 16))
+    for s, nitems, mcap, nlevels in ((side, 1, 8, 8), (None, 1, 8, 8), (side, 0, 8, 8), (side, 1, 0, 8), (side, 1, 8, 17)):
+        r = None if s is None else C.byref(s)
+        assert M.orbx_lastmatch_search_device(None, r, None, nitems, None, None, mcap, None, 1, tab, nlevels, 1, None, None, None,
+                                              None) == _lib.ORBX_E_INVALID
+        assert M.orbx_lastmatch_search(None, r, None, nitems, None, None, mcap, None, 1, tab, nlevels, 1, None, None, None) == _lib.ORBX_E_INVALID
+    M.orbx_lastmatch_destroy(None)
+
+
+@abi_util.needs_hipcc
+def test_lastmatch_kernels_compile_without_scratch():
+    from orb_slam3_modified_amd.build import LASTMATCH_SOURCE
+    scratch = abi_util.kernel_scratch(LASTMATCH_SOURCE, hidden=True)
+    assert len([n for n in scratch if "k_last_match" in n]) == 2 and len(scratch) == 2      # the LDS instantiation and the global-memory one
+    assert all(v == 0 for v in scratch.values()), scratch
+
+
+@abi_util.needs_hipcc
+def test_the_lds_instantiation_reads_lds_and_the_gate_is_not_fused():
+    """One template instantiation per path: the LDS one stages the frame's descriptors by LDS-DMA and reads records, descriptors and
+    candidates with ds_ instructions; nothing is a flat access; no float32 operation was fused, the gate's u - mbf * invz among them (a
+    v_mul_f32 and a v_sub_f32 stand in its place); the chain's reduction is DPP."""
+    from orb_slam3_modified_amd.build import LASTMATCH_SOURCE
+    asm = abi_util.device_asm(LASTMATCH_SOURCE, hidden=True)
+    assert "flat_load" not in asm and "flat_store" not in asm and "flat_atomic" not in asm
+    assert not re.search(FUSED_F32, asm)
+    assert re.search(FUSED_F32, "v_fma_f32 v1, v2, v3, v4") and re.search(FUSED_F32, "v_fmac_f32_e32 v1, v2, v3") and re.search(FUSED_F32, "v_mad_f32 v1")
+    assert not re.search(FUSED_F32, "v_mad_u32_u24 v1, v2, v3, v4") and not re.search(FUSED_F32, "v_mad_u64_u32 v[1:2]")
+    lds = asm[asm.index("k_last_matchILb1E"):]
+    lds = lds[:lds.index("s_endpgm")]
+    assert "global_load_lds_dwordx4" in lds and "ds_read_b128" in lds
+    assert "v_mul_f32" in lds and "v_sub_f32" in lds
+    assert "row_mirror" in lds or "row_half_mirror" in lds
+    glob = asm[asm.index("k_last_matchILb0E"):]
+    glob = glob[:glob.index("s_endpgm")]
+    assert "global_load_lds" not in glob and "global_load_dwordx4" in glob
+    assert "v_mul_f32" in glob and "v_sub_f32" in glob
