@@ -25,6 +25,7 @@ SCORE_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_score.so")    
 FISHEYE_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_fisheye.so")       # the batched two-camera rig front-end (include/orbx_fisheye.h)
 LOCALMATCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_localmatch.so")   # the batched SearchLocalPoints (include/orbx_localmatch.h)
 LASTMATCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_lastmatch.so")     # the batched SearchByProjection(Frame, LastFrame) (include/orbx_lastmatch.h)
+PROJMATCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_projmatch.so")     # the batched relocalization and Sim3 SearchByProjection (include/orbx_projmatch.h)
 
 ORBX_OK, ORBX_E_INVALID, ORBX_E_EMPTY, ORBX_E_DEVICE, ORBX_E_CAPACITY, ORBX_E_FORMAT = 0, -1, -2, -3, -4, -5
 NUM_KERNELS = 6
@@ -454,9 +455,31 @@ def lastmatch_lib(path: str = LASTMATCH_LIB_PATH) -> C.CDLL:
     return M
 
 
+class OrbxProjMatchSide(C.Structure):
+    """orbx_projmatch_side (include/orbx_projmatch.h)."""
+    _fields_ = [("d_kps", C.c_void_p), ("d_desc", C.c_void_p), ("d_counts", C.c_void_p), ("d_bounds", C.c_void_p), ("nframes", C.c_int),
+                ("capacity", C.c_int)]
+
+
+def projmatch_lib(path: str = PROJMATCH_LIB_PATH) -> C.CDLL:
+    """liborbx_projmatch.so.  `_orbx_projmatch_symbols`: every name of include/orbx_projmatch.h, bound here with its signature.  `path`: a
+    timing build of the same source (tools/projmatch_times.py)."""
+    vp, i32, sp, fp = C.c_void_p, C.c_int, C.POINTER(OrbxProjMatchSide), C.POINTER(C.c_float)
+    sig = {
+        "orbx_projmatch_create": (i32, [C.POINTER(vp), i32]),
+        "orbx_projmatch_destroy": (None, [vp]),
+        "orbx_projmatch_last_error": (C.c_char_p, [vp]),
+        "orbx_projmatch_search_device": (i32, [vp, sp, vp, i32, vp, vp, i32, vp, i32, fp, i32, i32, vp, vp, vp, vp]),
+        "orbx_projmatch_search": (i32, [vp, sp, vp, i32, vp, vp, i32, vp, i32, fp, i32, i32, vp, vp, vp]),
+    }
+    M = _load_side(path, sig)
+    M._orbx_projmatch_symbols = tuple(sig)
+    return M
+
+
 class SideHandle:
     """A handle of a side library whose entry points are <prefix>_create / _destroy / _last_error (StereoBatch, BowBatch, MatchBatch,
-    InitMatchBatch, TriMatchBatch, FuseBatch, DistinctBatch, ScoreBatch, FisheyeBatch, LocalMatchBatch, LastMatchBatch)."""
+    InitMatchBatch, TriMatchBatch, FuseBatch, DistinctBatch, ScoreBatch, FisheyeBatch, LocalMatchBatch, LastMatchBatch, ProjMatchBatch)."""
 
     def __init__(self, library: C.CDLL, prefix: str, *create_args):
         self._L, self._prefix, self._h = library, prefix, C.c_void_p(0)

@@ -240,6 +240,71 @@ class ORBmatcher:
                                                      ptr(match), C.byref(n)), self._ctx)
         return n.value, match[:len(k)].copy()
 
+    def _projection_chain(self, F, pp, th: float, up: int, max_dist, histogram: bool):
+        """What the relocalization and the Sim3 overloads share: the windows of the live points at levels [level - 1, level + up] through
+        WindowSearchGrid, then the host chain over the lists in point order: a keypoint that holds a map point (F.kp_taken) or was bound by
+        an earlier point is passed over, the best only, accepted iff (float)bestDist <= max_dist."""
+        k = np.ascontiguousarray(F.mvKeysUn)
+        d = np.ascontiguousarray(F.mDescriptors, np.uint8).reshape(-1, 32)
+        sf = np.ascontiguousarray(F.mvScaleFactors, np.float32)
+        match = np.full(len(k), -1, np.int32)
+        taken = np.zeros(len(k), bool) if getattr(F, "kp_taken", None) is None else np.array(F.kp_taken, bool).reshape(len(k))
+        u, v, ang = (np.ascontiguousarray(pp[key], np.float32) for key in ("u", "v", "angle"))
+        level = np.ascontiguousarray(pp["level"], np.int32)
+        pd = np.ascontiguousarray(pp["desc"], np.uint8).reshape(-1, 32)
+        owner = np.nonzero((np.asarray(pp["valid"]) != 0) & np.isfinite(u) & np.isfinite(v))[0]
+        if len(owner) == 0 or len(k) == 0:
+            return 0, match
+        min_x, min_y, max_x, max_y = (np.float32(b) for b in F.bounds)
+        grid = dict(min_x=min_x, min_y=min_y, inv_w=np.float32(64) / np.float32(max_x - min_x), inv_h=np.float32(48) / np.float32(max_y - min_y))
+        lv = level[owner]
+        L = self.WindowSearchGrid(k, d, grid, u[owner], v[owner], np.float32(th) * sf[lv], lv - 1, lv + up, pd[owner])
+        rp, cand, dist = L["row_ptr"], L["cand"], L["dist"]
+        limit, factor = np.float32(max_dist), np.float32(1.0) / np.float32(self.HISTO_LENGTH)
+        bins = [[] for _ in range(self.HISTO_LENGTH)]
+        nmatches = 0
+        for q, i in enumerate(owner):
+            best, idx = 256, -1
+            for c in range(rp[q], rp[q + 1]):
+                if not taken[cand[c]] and dist[c] < best:
+                    best, idx = int(dist[c]), int(cand[c])
+            if idx < 0 or not np.float32(best) <= limit:
+                continue
+            match[idx], taken[idx] = i, True
+            nmatches += 1
+            if histogram:
+                with np.errstate(all="ignore"):
+                    rot = np.float32(ang[i] - k["angle"][idx])
+                    if rot < 0.0:
+                        rot = np.float32(rot + np.float32(360.0))
+                    r = np.float32(rot * factor)
+                if np.isfinite(r):
+                    b = int(np.floor(float(r) + 0.5)) if r >= 0 else int(np.ceil(float(r) - 0.5))
+                    b = 0 if b == self.HISTO_LENGTH else b
+                    if 0 <= b < self.HISTO_LENGTH:
+                        bins[b].append(idx)
+        if histogram:
+            keep = self.ComputeThreeMaxima([len(b) for b in bins])
+            for b in range(self.HISTO_LENGTH):
+                if b not in keep:
+                    for idx in bins[b]:
+                        match[idx] = -2
+                        nmatches -= 1
+        return nmatches, match
+
+    def SearchByProjectionReloc(self, F, pp, th: float, ORBdist: int):
+        """ORBmatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (src/ORBmatcher.cc:1889-2010), Nleft == -1, after
+        the caller's projection step.  F: frame-like with mvKeysUn, mDescriptors, bounds, mvScaleFactors and kp_taken ([n], nonzero: the
+        keypoint holds a map point; None: none does; not changed).  pp: dict of arrays valid, u, v, angle, level, desc, one entry per map
+        point of the keyframe.  Returns (nmatches, kp_match [n]: -1 untouched / i bound / -2 cleared by the rotation filter)."""
+        return self._projection_chain(F, pp, th, 1, np.float32(ORBdist), self.mbCheckOrientation)
+
+    def SearchByProjectionSim3(self, KF, pp, th: int, ratioHamming: float):
+        """ORBmatcher::SearchByProjection(pKF, Scw, vpPoints[, vpPointsKFs], vpMatched[, vpMatchedKF], th, ratioHamming)
+        (src/ORBmatcher.cc:427-532, :534-646) after the caller's projection step; KF and pp as in SearchByProjectionReloc (kp_taken:
+        vpMatched[idx] non-NULL; angle is not read).  Returns (nmatches, kp_match [n]); vpMatchedKF is read off kp_match."""
+        return self._projection_chain(KF, pp, th, 0, np.float32(self.TH_LOW) * np.float32(ratioHamming), False)
+
     def SearchByBoW(self, kf_desc, kf_angle, kf_valid, kf_fv, f_desc, f_angle, f_fv):
         """ORBmatcher::SearchByBoW(KeyFrame*, Frame&, vpMapPointMatches) (src/ORBmatcher.cc:223-425), single-camera.
         kf_fv / f_fv: DBoW2::FeatureVector as dict node -> list of feature indices.  Returns (nmatches, match_kf [nf])."""

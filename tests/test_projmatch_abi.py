@@ -1,0 +1,148 @@
+"""include/orbx_projmatch.h <-> liborbx_projmatch.so: the batched relocalization and Sim3 matchers are a library of their own beside the
+product (CPU-only checks)."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+from tests import abi_util
+from tests.abi_util import declared as _declared, exported as _exported
+
+ROOT = abi_util.ROOT
+KERNELS_HASH = "cfa5f580d25d496f"   # the product's kernel sources: this library changes none of them
+HEADER = "orbx_projmatch.h"
+NAMES = ("create", "destroy", "last_error", "search_device", "search")
+FUSED_F32 = r"v_(pk_)?(fma|fmac|fmaak|fmamk|mad|madak|madmk)_f32"
+
+
+def test_build_produces_the_projmatch_library():
+    from orb_slam3_modified_amd import _lib, build
+    build.build()
+    assert os.path.isfile(build.PROJMATCH_OUT) and build.PROJMATCH_OUT == _lib.PROJMATCH_LIB_PATH
+    assert os.path.dirname(build.PROJMATCH_OUT) == os.path.dirname(_lib.LIB_PATH) == os.path.join(ROOT, "orb_slam3_modified_amd")
+    assert os.path.basename(build.PROJMATCH_OUT) == "liborbx_projmatch.so"
+    assert HEADER in build.HEADERS
+    rec = [l for l in build.LIBS if l.out == build.PROJMATCH_OUT]
+    assert len(rec) == 1 and rec[0].sources == (build.PROJMATCH_SOURCE,) and rec[0].hidden
+    assert "-ffp-contract=off" in build.FLAGS       # the radius' and the grid's float expressions are not contracted
+
+
+def test_projmatch_library_exports_exactly_its_header():
+    from orb_slam3_modified_amd import _lib, build
+    build.build()
+    names = _declared(HEADER)
+    assert names == sorted("orbx_projmatch_" + n for n in NAMES), names
+    exported = _exported(_lib.PROJMATCH_LIB_PATH)
+    assert {e for e in exported if e.startswith("orbx_")} == set(names)
+    assert not [e for e in exported if not e.startswith("orbx_projmatch_") and not e.startswith("_")], sorted(exported)[:10]   # -fvisibility=hidden
+
+
+def test_every_other_library_keeps_its_abi_and_the_product_its_kernels():
+    from orb_slam3_modified_amd import _lib, build
+    build.build()
+    names = set(_declared(HEADER))
+    others = [l.out for l in build.LIBS if l.out != build.PROJMATCH_OUT]
+    assert len(others) == len(build.LIBS) - 1 and _lib.LIB_PATH in others and _lib.LASTMATCH_LIB_PATH in others
+    for other in others:
+        assert not names & _exported(other), other
+    for header in build.HEADERS:
+        if header != HEADER:
+            assert not names & set(_declared(header)), header
+    assert len(_declared("orbx.h")) == 100
+    assert build.kernels_hash() == KERNELS_HASH
+    assert os.path.dirname(build.PROJMATCH_SOURCE) == "projmatch" and "orbx_projmatch.hip" not in os.listdir(build.CSRC)
+    src = open(os.path.join(build.CSRC, build.PROJMATCH_SOURCE)).read()
+    assert "side/orbx_handle.h" in src and "side/orbx_pair_device.h" in src and "orbx_internal.h" not in src
+    assert "orbx_lastmatch" not in src.replace("csrc/lastmatch/orbx_lastmatch.hip", "")   # nothing of the last-frame matcher is included or called
+
+
+@pytest.mark.skipif(shutil.which("gcc") is None, reason="gcc not installed")
+def test_the_header_compiles_as_c(tmp_path):
+    src = tmp_path / "use.c"
+    src.write_text('#include "orbx_projmatch.h"\nint main(void) { orbx_projmatch_point q; orbx_projmatch_side s; orbx_projmatch_item i; '
+                   'return (int)sizeof(q) - 32 + (int)sizeof(s) - 40 + (int)sizeof(i) - 16; }\n'
+                   'typedef char point_is_32[sizeof(orbx_projmatch_point) == 32 ? 1 : -1];\n'
+                   'typedef char item_is_16[sizeof(orbx_projmatch_item) == 16 ? 1 : -1];\n'
+                   'typedef char side_is_40[sizeof(orbx_projmatch_side) == 4 * sizeof(void*) + 8 ? 1 : -1];\n')
+    exe = tmp_path / "use.o"
+    p = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), "-c", str(src), "-o", str(exe)],
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert p.returncode == 0, p.stdout[-2000:]
+
+
+def test_python_binding_covers_the_header():
+    from orb_slam3_modified_amd import _lib, build
+    build.build()
+    M = _lib.projmatch_lib()
+    assert set(M._orbx_projmatch_symbols) == set(_declared(HEADER))
+    from orb_slam3_modified_amd import lastmatch, projmatch
+    assert issubclass(projmatch.ProjMatchBatch, _lib.SideHandle)
+    for m in ("search_device", "search"):
+        assert callable(getattr(projmatch.ProjMatchBatch, m))
+    # the structures the binding passes are the header's: the same fields, in order and size; the side is lastmatch's without d_uright
+    in_header = abi_util.struct_fields(HEADER, "orbx_projmatch_side")
+    assert in_header == [f for f, _ in _lib.OrbxProjMatchSide._fields_]
+    assert in_header == [f for f in abi_util.struct_fields("orbx_lastmatch.h", "orbx_lastmatch_side") if f != "d_uright"]
+    assert C.sizeof(_lib.OrbxProjMatchSide) == 4 * 8 + 2 * 4
+    text = open(os.path.join(ROOT, "include", HEADER)).read()
+    names = list(projmatch.POINT_DTYPE.names)
+    assert names[-1] == "pad" and projmatch.POINT_DTYPE["pad"].shape == (2,) and "  int32_t pad[2];\n" in text
+    assert abi_util.struct_fields(HEADER, "orbx_projmatch_point") == names[:-1] and projmatch.POINT_DTYPE.itemsize == 32
+    assert [projmatch.POINT_DTYPE.fields[n][1] for n in names] == [0, 4, 8, 12, 16, 20, 24]
+    assert [projmatch.POINT_DTYPE[n].base.str for n in names] == ["<f4"] * 3 + ["<i4"] * 4
+    assert abi_util.struct_fields(HEADER, "orbx_projmatch_item") == list(projmatch.ITEM_DTYPE.names) and projmatch.ITEM_DTYPE.itemsize == 16
+    assert [projmatch.ITEM_DTYPE[n].str for n in projmatch.ITEM_DTYPE.names] == ["<i4", "<i4", "<f4", "<f4"]
+    # the accept limits as the reference forms them
+    assert projmatch.max_dist_reloc(64) == 64.0 and projmatch.max_dist_sim3(1.5) == 75.0 and projmatch.max_dist_sim3(1.0) == 50.0
+    # the sizing formula the binding states is the library's (the layout is lastmatch's): EuRoC's capacity with 2048 points fits the LDS
+    # with room for more than 16 000 candidates, the initialisation extractor's capacity does not fit
+    assert projmatch.lds_bytes(1024, 2048) + 4 * 16000 <= projmatch.LDS_MAX < projmatch.lds_bytes(5024, 1024)
+    assert projmatch.lds_bytes(1024, 2048) == lastmatch.lds_bytes(1024, 2048)
+    src = open(os.path.join(build.CSRC, build.PROJMATCH_SOURCE)).read()
+    assert "kLdsMax = 148 * 1024" in src and '"ORBX_PROJMATCH_LDS"' in src
+    # the header states what is out of scope, what is undefined and the reference's lines
+    for word in ("two-camera block", "PredictScale", "non-finite", "asserts", "mo_window_search_grid", "ORBX_PROJMATCH_LDS", "ComputeThreeMaxima",
+                 ":1889-2010", ":427-532", ":534-646", "src/KeyFrame.cc:704-748", "at most once", "NaN max_dist", "index [-1]"):
+        assert word in text, word
+
+
+def test_bad_arguments_are_rejected_without_a_device():
+    """Argument checks that come before any device call, both forms."""
+    from orb_slam3_modified_amd import _lib
+    M = _lib.projmatch_lib()
+    h = C.c_void_p(0)
+    assert M.orbx_projmatch_create(None, 0) == _lib.ORBX_E_INVALID
+    assert b"null" in M.orbx_projmatch_last_error(None)
+    assert M.orbx_projmatch_create(C.byref(h), -1) == _lib.ORBX_E_INVALID and not h.value
+    assert b"device" in M.orbx_projmatch_last_error(None)
+    side = _lib.OrbxProjMatchSide()
+    tab = (C.c_float * 16)(*([1.0] * 16))
+    for s, nitems, mcap, nlevels in ((side, 1, 8, 8), (None, 1, 8, 8), (side, 0, 8, 8), (side, 1, 0, 8), (side, 1, 8, 17)):
+        r = None if s is None else C.byref(s)
+        assert M.orbx_projmatch_search_device(None, r, None, nitems, None, None, mcap, None, 1, tab, nlevels, 1, None, None, None,
+                                              None) == _lib.ORBX_E_INVALID
+        assert M.orbx_projmatch_search(None, r, None, nitems, None, None, mcap, None, 1, tab, nlevels, 1, None, None, None) == _lib.ORBX_E_INVALID
+    M.orbx_projmatch_destroy(None)
+
+
+@abi_util.needs_hipcc
+def test_projmatch_kernels_compile_without_scratch():
+    from orb_slam3_modified_amd.build import PROJMATCH_SOURCE
+    scratch = abi_util.kernel_scratch(PROJMATCH_SOURCE, hidden=True)
+    assert len([n for n in scratch if "k_proj_match" in n]) == 2 and len(scratch) == 2      # the LDS instantiation and the global-memory one
+    assert all(v == 0 for v in scratch.values()), scratch
+
+
+@abi_util.needs_hipcc
+def test_no_float32_operation_of_the_code_object_is_fused():
+    """The radius th * sf and the grid's (x - min_x) * inv_w stand as the specification states them: no fused float32 multiply-add in the
+    gfx950 code object of the new source."""
+    from orb_slam3_modified_amd.build import PROJMATCH_SOURCE
+    asm = abi_util.device_asm(PROJMATCH_SOURCE, hidden=True)
+    assert "k_proj_matchILb1E" in asm and "k_proj_matchILb0E" in asm
+    assert not re.search(FUSED_F32, asm)
+    assert re.search(FUSED_F32, "v_fma_f32 v1, v2, v3, v4") and re.search(FUSED_F32, "v_fmac_f32_e32 v1, v2, v3") and re.search(FUSED_F32, "v_mad_f32 v1")
+    assert not re.search(FUSED_F32, "v_mad_u32_u24 v1, v2, v3, v4") and not re.search(FUSED_F32, "v_mad_u64_u32 v[1:2]")
