@@ -27,6 +27,8 @@ LOCALMATCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_localmatc
 LASTMATCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_lastmatch.so")     # the batched SearchByProjection(Frame, LastFrame) (include/orbx_lastmatch.h)
 PROJMATCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_projmatch.so")     # the batched relocalization and Sim3 SearchByProjection (include/orbx_projmatch.h)
 
+PLACE_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_place.so")             # the batched place recognition (include/orbx_place.h)
+
 ORBX_OK, ORBX_E_INVALID, ORBX_E_EMPTY, ORBX_E_DEVICE, ORBX_E_CAPACITY, ORBX_E_FORMAT = 0, -1, -2, -3, -4, -5
 NUM_KERNELS = 6
 
@@ -477,9 +479,38 @@ def projmatch_lib(path: str = PROJMATCH_LIB_PATH) -> C.CDLL:
     return M
 
 
+class OrbxPlaceDb(C.Structure):
+    """orbx_place_db (include/orbx_place.h)."""
+    _fields_ = [("d_ids", C.c_void_p), ("d_vals", C.c_void_p), ("d_n", C.c_void_p), ("d_kf_map", C.c_void_p), ("d_kf_cov", C.c_void_p),
+                ("d_kf_score", C.c_void_p), ("count", C.c_int), ("stride", C.c_int)]
+
+
+class OrbxPlaceQueries(C.Structure):
+    """orbx_place_queries (include/orbx_place.h)."""
+    _fields_ = [("d_ids", C.c_void_p), ("d_vals", C.c_void_p), ("d_n", C.c_void_p), ("d_q_map", C.c_void_p), ("d_excl_ptr", C.c_void_p),
+                ("d_excl_idx", C.c_void_p), ("count", C.c_int), ("stride", C.c_int), ("n_excl", C.c_int)]
+
+
+def place_lib(path: str = PLACE_LIB_PATH) -> C.CDLL:
+    """liborbx_place.so.  `_orbx_place_symbols`: every name of include/orbx_place.h, bound here with its signature.  `path`: a timing build
+    of the same source (tools/place_times.py)."""
+    vp, i32, dp, qp = C.c_void_p, C.c_int, C.POINTER(OrbxPlaceDb), C.POINTER(OrbxPlaceQueries)
+    sig = {
+        "orbx_place_create": (i32, [C.POINTER(vp), i32]),
+        "orbx_place_destroy": (None, [vp]),
+        "orbx_place_last_error": (C.c_char_p, [vp]),
+        "orbx_place_query_device": (i32, [vp, i32, i32, dp, qp, i32, vp, vp, vp, vp, vp, vp]),
+        "orbx_place_query": (i32, [vp, i32, i32, dp, qp, i32, vp, vp, vp, vp, vp]),
+    }
+    M = _load_side(path, sig)
+    M._orbx_place_symbols = tuple(sig)
+    return M
+
+
 class SideHandle:
     """A handle of a side library whose entry points are <prefix>_create / _destroy / _last_error (StereoBatch, BowBatch, MatchBatch,
-    InitMatchBatch, TriMatchBatch, FuseBatch, DistinctBatch, ScoreBatch, FisheyeBatch, LocalMatchBatch, LastMatchBatch, ProjMatchBatch)."""
+    InitMatchBatch, TriMatchBatch, FuseBatch, DistinctBatch, ScoreBatch, FisheyeBatch, LocalMatchBatch, LastMatchBatch, ProjMatchBatch,
+    PlaceBatch)."""
 
     def __init__(self, library: C.CDLL, prefix: str, *create_args):
         self._L, self._prefix, self._h = library, prefix, C.c_void_p(0)

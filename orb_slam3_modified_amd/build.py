@@ -17,6 +17,8 @@ LIBS is the one place that knows them, one record per library; what is stale, wh
   liborbx_localmatch.so the batched SearchLocalPoints (include/orbx_localmatch.h)
   liborbx_lastmatch.so  the batched SearchByProjection(Frame, LastFrame) (include/orbx_lastmatch.h)
   liborbx_projmatch.so  the batched relocalization and Sim3 SearchByProjection (include/orbx_projmatch.h)
+  liborbx_place.so      the batched place recognition: relocalization and N-best candidates (include/orbx_place.h); takes nothing from
+                        the product
 The libraries beside the product link liborbx.so and use its ABI (and orbx_internal.h where they read a context's buffers).  Their sources sit
 in subdirectories of csrc/, outside kernels_hash(): the committed counter files measure the product's kernels, which they do not change.
 A new one is one more record ("Adding a side library")."""
@@ -59,6 +61,8 @@ LASTMATCH_OUT = os.path.join(os.path.dirname(OUT), "liborbx_lastmatch.so")
 LASTMATCH_SOURCE = os.path.join("lastmatch", "orbx_lastmatch.hip")
 PROJMATCH_OUT = os.path.join(os.path.dirname(OUT), "liborbx_projmatch.so")
 PROJMATCH_SOURCE = os.path.join("projmatch", "orbx_projmatch.hip")
+PLACE_OUT = os.path.join(os.path.dirname(OUT), "liborbx_place.so")
+PLACE_SOURCE = os.path.join("place", "orbx_place.hip")
 
 
 class Lib(NamedTuple):
@@ -83,10 +87,11 @@ LIBS = (Lib(OUT, tuple(SOURCES)),
         Lib(FISHEYE_OUT, (FISHEYE_SOURCE,), hidden=True, product=True),
         Lib(LOCALMATCH_OUT, (LOCALMATCH_SOURCE,), hidden=True, product=True),
         Lib(LASTMATCH_OUT, (LASTMATCH_SOURCE,), hidden=True, product=True),
-        Lib(PROJMATCH_OUT, (PROJMATCH_SOURCE,), hidden=True, product=True))
+        Lib(PROJMATCH_OUT, (PROJMATCH_SOURCE,), hidden=True, product=True),
+        Lib(PLACE_OUT, (PLACE_SOURCE,), hidden=True))
 HEADERS = ("orbx.h", "orbx_debug.h", "orbx_train.h", "orbx_stereo.h", "orbx_bow.h", "orbx_match.h", "orbx_initmatch.h", "orbx_trimatch.h",
            "orbx_fuse.h", "orbx_mpdesc.h", "orbx_score.h", "orbx_fisheye.h", "orbx_localmatch.h", "orbx_lastmatch.h",
-           "orbx_projmatch.h")
+           "orbx_projmatch.h", "orbx_place.h")
 # -ffp-contract=off: the float paths (fastAtan2 polynomial, BRIEF rotation) must not be fused into FMAs,
 # the CPU reference evaluates them as separate IEEE operations (DESIGN.md "bit-exactness").
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall",

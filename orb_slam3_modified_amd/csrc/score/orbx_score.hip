@@ -24,6 +24,7 @@
 #include <limits>
 #include <string>
 
+#include "../side/orbx_bowvec_device.h"
 #include "../side/orbx_handle.h"
 #include "../../../include/orbx_score.h"
 
@@ -38,12 +39,8 @@ static_assert(kTile % kWaves == 0, "every wave the same number of pairs");
 enum : int { kL1 = ORBX_SCORE_L1_NORM, kL2 = ORBX_SCORE_L2_NORM, kChi = ORBX_SCORE_CHI_SQUARE, kKL = ORBX_SCORE_KL,
              kBha = ORBX_SCORE_BHATTACHARYYA, kDot = ORBX_SCORE_DOT_PRODUCT };
 
-// one side of the matrix: fixed stride with counts (n), or compact CSR (ptr)
-struct Side { const uint32_t* ids; const double* vals; const int32_t* n; const int32_t* ptr; int stride; };
-__device__ __forceinline__ void side_row(const Side& s, int i, size_t* start, int* n) {
-  if (s.ptr) { *start = (size_t)s.ptr[i]; *n = s.ptr[i + 1] - s.ptr[i]; }      // ascending from >= 0: checked on the host
-  else { *start = (size_t)i * s.stride; *n = min(max(s.n[i], 0), s.stride); }
-}
+using orbx::side::Side;
+using orbx::side::side_row;
 
 // the term of one common word; false: the word adds nothing (CHI_SQUARE's vi + wi == 0)
 template <int S>
@@ -79,11 +76,7 @@ __device__ __forceinline__ double score_pair_wave(const uint32_t* qi, const doub
     double t = 0;
     if (j < dn) {
       const uint32_t id = di[j];
-      int lo = 0, len = qn;               // lower_bound: the first query entry whose id is not below `id`
-      while (len > 0) {
-        const int half = len >> 1;
-        if (qi[lo + half] < id) { lo += half + 1; len -= half + 1; } else len = half;
-      }
+      const int lo = orbx::side::first_not_below(qi, qn, id);
       if (lo < qn && qi[lo] == id) hit = score_term<S>(qv[lo], dv[j], &t);
     }
     unsigned long long m = __ballot(hit);
@@ -111,21 +104,7 @@ __global__ __launch_bounds__(kThreads) void k_score(Side q, Side db, int ndb, in
   const bool staged = qn <= lds_limit;    // uniform over the workgroup
   int mi = 0, mv = 0;
   if (staged) {
-    mi = (int)(((uintptr_t)gi >> 2) & 3);
-    mv = (int)(((uintptr_t)gv >> 3) & 1);
-    // chunk c of an image holds its elements 4c .. 4c + 3 (2c, 2c + 1): a chunk that lies inside the row is one 16-byte load
-    const uint4* const gi4 = (const uint4*)(gi - mi);
-    for (int c = tid; 4 * c < mi + qn; c += kThreads) {
-      if (4 * c >= mi && 4 * c + 4 <= mi + qn) ((uint4*)s_id)[c] = gi4[c];
-      else
-        for (int e = max(4 * c, mi); e < min(4 * c + 4, mi + qn); e++) s_id[e] = gi[e - mi];
-    }
-    const double2* const gv2 = (const double2*)(gv - mv);
-    for (int c = tid; 2 * c < mv + qn; c += kThreads) {
-      if (2 * c >= mv && 2 * c + 2 <= mv + qn) ((double2*)s_v)[c] = gv2[c];
-      else
-        for (int e = max(2 * c, mv); e < min(2 * c + 2, mv + qn); e++) s_v[e] = gv[e - mv];
-    }
+    orbx::side::stage_row(gi, gv, qn, s_id, s_v, tid, kThreads, &mi, &mv);
     __syncthreads();
   }
   for (int k = wave; k < kTile; k += kWaves) {
