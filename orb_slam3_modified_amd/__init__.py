@@ -6,4 +6,5 @@ from .vocabulary import ORBVocabulary  # noqa: F401
 from .kfdb import KeyFrameDatabase  # noqa: F401
 from .score import ScoreBatch  # noqa: F401
 from .place import PlaceBatch  # noqa: F401
+from .placeindex import PlaceIndex  # noqa: F401
 from ._lib import KP_DTYPE, OrbxError  # noqa: F401

@@ -28,6 +28,7 @@ LASTMATCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_lastmatch.
 PROJMATCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_projmatch.so")     # the batched relocalization and Sim3 SearchByProjection (include/orbx_projmatch.h)
 
 PLACE_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_place.so")             # the batched place recognition (include/orbx_place.h)
+PLACEINDEX_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_placeindex.so")   # the same through a device inverted file (include/orbx_placeindex.h)
 
 ORBX_OK, ORBX_E_INVALID, ORBX_E_EMPTY, ORBX_E_DEVICE, ORBX_E_CAPACITY, ORBX_E_FORMAT = 0, -1, -2, -3, -4, -5
 NUM_KERNELS = 6
@@ -507,10 +508,27 @@ def place_lib(path: str = PLACE_LIB_PATH) -> C.CDLL:
     return M
 
 
+def placeindex_lib(path: str = PLACEINDEX_LIB_PATH) -> C.CDLL:
+    """liborbx_placeindex.so.  `_orbx_placeindex_symbols`: every name of include/orbx_placeindex.h, bound here with its signature.  `path`: a
+    timing build of the same source (tools/placeindex_times.py)."""
+    vp, i32, dp, qp = C.c_void_p, C.c_int, C.POINTER(OrbxPlaceDb), C.POINTER(OrbxPlaceQueries)
+    sig = {
+        "orbx_placeindex_create": (i32, [C.POINTER(vp), i32, i32]),
+        "orbx_placeindex_destroy": (None, [vp]),
+        "orbx_placeindex_last_error": (C.c_char_p, [vp]),
+        "orbx_placeindex_sync_device": (i32, [vp, dp, vp]),
+        "orbx_placeindex_query_device": (i32, [vp, i32, i32, dp, qp, i32, vp, vp, vp, vp, vp, vp]),
+        "orbx_placeindex_query": (i32, [vp, i32, i32, dp, qp, i32, vp, vp, vp, vp, vp]),
+    }
+    M = _load_side(path, sig)
+    M._orbx_placeindex_symbols = tuple(sig)
+    return M
+
+
 class SideHandle:
     """A handle of a side library whose entry points are <prefix>_create / _destroy / _last_error (StereoBatch, BowBatch, MatchBatch,
     InitMatchBatch, TriMatchBatch, FuseBatch, DistinctBatch, ScoreBatch, FisheyeBatch, LocalMatchBatch, LastMatchBatch, ProjMatchBatch,
-    PlaceBatch)."""
+    PlaceBatch, PlaceIndex)."""
 
     def __init__(self, library: C.CDLL, prefix: str, *create_args):
         self._L, self._prefix, self._h = library, prefix, C.c_void_p(0)
