@@ -29,6 +29,7 @@ PROJMATCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_projmatch.
 
 PLACE_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_place.so")             # the batched place recognition (include/orbx_place.h)
 PLACEINDEX_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_placeindex.so")   # the same through a device inverted file (include/orbx_placeindex.h)
+FRUSTUM_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_frustum.so")         # the batched Frame::isInFrustum (include/orbx_frustum.h)
 
 ORBX_OK, ORBX_E_INVALID, ORBX_E_EMPTY, ORBX_E_DEVICE, ORBX_E_CAPACITY, ORBX_E_FORMAT = 0, -1, -2, -3, -4, -5
 NUM_KERNELS = 6
@@ -525,10 +526,29 @@ def placeindex_lib(path: str = PLACEINDEX_LIB_PATH) -> C.CDLL:
     return M
 
 
+def frustum_lib(path: str = FRUSTUM_LIB_PATH) -> C.CDLL:
+    """liborbx_frustum.so.  `_orbx_frustum_symbols`: every name of include/orbx_frustum.h, bound here with its signature.  `path`: a timing
+    build of the same source."""
+    vp, i32, f32 = C.c_void_p, C.c_int, C.c_float
+    call = [vp, vp, i32, vp, i32, vp, vp, i32, f32, i32, f32, i32, i32, vp, vp, vp]   # points .. ntomatch
+    sig = {
+        "orbx_frustum_create": (i32, [C.POINTER(vp), i32]),
+        "orbx_frustum_destroy": (None, [vp]),
+        "orbx_frustum_last_error": (C.c_char_p, [vp]),
+        "orbx_frustum_level_thresholds": (i32, [f32, i32, i32, vp]),
+        "orbx_frustum_project_device": (i32, [vp] + call + [vp]),
+        "orbx_frustum_project": (i32, [vp] + call),
+        "orbx_frustum_project_reference": (i32, call),
+    }
+    M = _load_side(path, sig)
+    M._orbx_frustum_symbols = tuple(sig)
+    return M
+
+
 class SideHandle:
     """A handle of a side library whose entry points are <prefix>_create / _destroy / _last_error (StereoBatch, BowBatch, MatchBatch,
     InitMatchBatch, TriMatchBatch, FuseBatch, DistinctBatch, ScoreBatch, FisheyeBatch, LocalMatchBatch, LastMatchBatch, ProjMatchBatch,
-    PlaceBatch, PlaceIndex)."""
+    PlaceBatch, PlaceIndex, FrustumBatch)."""
 
     def __init__(self, library: C.CDLL, prefix: str, *create_args):
         self._L, self._prefix, self._h = library, prefix, C.c_void_p(0)
