@@ -64,6 +64,7 @@ LASTMATCH_OUT = os.path.join(os.path.dirname(OUT), "liborbx_lastmatch.so")
 LASTMATCH_SOURCE = os.path.join("lastmatch", "orbx_lastmatch.hip")
 PROJMATCH_OUT = os.path.join(os.path.dirname(OUT), "liborbx_projmatch.so")
 PROJMATCH_SOURCE = os.path.join("projmatch", "orbx_projmatch.hip")
+WINDOW_CORE = (os.path.join("side", "orbx_window_device.h"), os.path.join("side", "orbx_window_host.h"))   # what those three share
 PLACE_OUT = os.path.join(os.path.dirname(OUT), "liborbx_place.so")
 PLACE_SOURCE = os.path.join("place", "orbx_place.hip")
 PLACE_KERNELS = os.path.join("place", "orbx_place_kernels.h")   # what the two place libraries share
@@ -93,9 +94,9 @@ LIBS = (Lib(OUT, tuple(SOURCES)),
         Lib(MPDESC_OUT, (MPDESC_SOURCE,), hidden=True, product=True),
         Lib(SCORE_OUT, (SCORE_SOURCE,), hidden=True),
         Lib(FISHEYE_OUT, (FISHEYE_SOURCE,), hidden=True, product=True),
-        Lib(LOCALMATCH_OUT, (LOCALMATCH_SOURCE,), hidden=True, product=True),
-        Lib(LASTMATCH_OUT, (LASTMATCH_SOURCE,), hidden=True, product=True),
-        Lib(PROJMATCH_OUT, (PROJMATCH_SOURCE,), hidden=True, product=True),
+        Lib(LOCALMATCH_OUT, (LOCALMATCH_SOURCE,), hidden=True, product=True, deps=WINDOW_CORE),
+        Lib(LASTMATCH_OUT, (LASTMATCH_SOURCE,), hidden=True, product=True, deps=WINDOW_CORE),
+        Lib(PROJMATCH_OUT, (PROJMATCH_SOURCE,), hidden=True, product=True, deps=WINDOW_CORE),
         Lib(PLACE_OUT, (PLACE_SOURCE,), hidden=True, deps=(PLACE_KERNELS,)),
         Lib(PLACEINDEX_OUT, (PLACEINDEX_SOURCE,), hidden=True, deps=(PLACE_KERNELS,)),
         Lib(FRUSTUM_OUT, (FRUSTUM_SOURCE,), hidden=True))

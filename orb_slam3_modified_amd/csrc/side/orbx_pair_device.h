@@ -1,10 +1,10 @@
-// The device helpers the batched pair matchers share (liborbx_match.so, liborbx_initmatch.so): descriptors and Hamming distances, the wave
-// minimum, the 32-bit top-2 keys (liborbx_fisheye.so), a chain's relaxed loads and stores, the rotation bin, the keypoint field reader, the LDS-DMA staging,
-// the frame grid's record (liborbx_fuse.so, liborbx_localmatch.so), a work list's pop (liborbx_trimatch.so) and the workgroup scan
-// (liborbx_bow.so, liborbx_fisheye.so).  Device code only; it
-// sits below csrc/, outside kernels_hash().  A kernel's file imports the names with `using namespace orbx::side::dev;` inside its anonymous
-// namespace.  ComputeThreeMaxima and the trip loop's three-reduction merge stay written out in both kernels: as functions of this header
-// they change the kernels' instruction streams (the compiler unrolls and schedules them differently).
+// The device helpers the side libraries' matching kernels share: descriptors and Hamming distances, the wave minimum, the 32-bit top-2
+// keys, a chain's relaxed loads and stores, the rotation bin, the keypoint field reader, the LDS-DMA staging, a frame grid's record, a work
+// list's pop and the workgroup scan.  Every source below csrc/ that includes this file is a user; the frame grid and the window of the
+// three chained projection matchers are built on it in orbx_window_device.h.  Device code only; it sits below csrc/, outside
+// kernels_hash().  A kernel's file imports the names with `using namespace orbx::side::dev;` inside its anonymous namespace.
+// ComputeThreeMaxima and the trip loop's three-reduction merge stay written out in k_match_pairs and k_init_pairs: as functions of this
+// header they change those kernels' instruction streams (the compiler unrolls and schedules them differently).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -18,7 +18,7 @@ namespace dev {
 
 struct D8 { uint32_t w[8]; };
 
-// a sorted position's record in a frame grid (liborbx_fuse.so, liborbx_localmatch.so): what a window test reads of its keypoint
+// a sorted position's record in a frame grid (k_fuse_search, orbx_window_device.h): what a window test reads of its keypoint
 struct __align__(16) Rec { float x, y; int32_t octave; float ur; };
 
 __device__ __forceinline__ D8 load_desc(const uint8_t* p) {

@@ -12,29 +12,13 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
+from ._window import LDS_MAX, MAX_CAPACITY, MAX_LEVELS, _table, _up16, lds_bytes  # noqa: F401  (re-exported)
 from ._lib import KP_DTYPE, OrbxLastMatchSide, addr, host_array as arr, host_view, ptr
 
-LDS_MAX = 148 * 1024     # the largest dynamic LDS block of a workgroup (ORBX_LASTMATCH_LDS lowers it)
-MAX_CAPACITY = 32768
-MAX_LEVELS = 16
 ITEM_DTYPE = np.dtype([("frame", "<i4"), ("direction", "<i4"), ("mbf", "<f4"), ("th", "<f4")])
 POINT_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("invz", "<f4"), ("angle", "<f4"), ("octave", "<i4"), ("obs", "<i4"), ("point", "<i4"),
                         ("valid", "<i4")])
 assert ITEM_DTYPE.itemsize == 16 and POINT_DTYPE.itemsize == 32
-
-
-def _up16(n: int) -> int:
-    return (n + 15) & ~15
-
-
-def lds_bytes(capacity: int, mcap: int) -> int:
-    """What the LDS path needs beside the candidate room for frames of this capacity and rows of up to `mcap` points: descriptors, sorted
-    keys, records, cell starts, offsets, the points' results.  A search takes the LDS path when this plus one list of `capacity` candidates
-    is within the handle's limit; the rest of the limit is candidate room (4 bytes a candidate)."""
-    p2 = 2
-    while p2 < capacity:
-        p2 <<= 1
-    return sum(_up16(b) for b in (32 * capacity, 4 * p2, 16 * capacity, 2 * (64 * 48 + 1), 4 * (mcap + 1), 4 * mcap))
 
 
 @dataclass
@@ -77,11 +61,6 @@ class LastMatchResult:
 
     def __getitem__(self, b: int):
         return int(host_view(self.nmatches[b:b + 1])[0]), host_view(self.kp_match[b]), host_view(self.kp_obs[b])
-
-
-def _table(scale_factors):
-    s = np.ascontiguousarray(scale_factors, np.float32).ravel()
-    return s, s.ctypes.data_as(C.POINTER(C.c_float)), len(s)
 
 
 class LastMatchBatch(_lib.SideHandle):

@@ -13,11 +13,9 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
+from ._window import LDS_MAX, MAX_CAPACITY, MAX_LEVELS, _table, _up16, lds_bytes  # noqa: F401  (re-exported)
 from ._lib import KP_DTYPE, OrbxProjMatchSide, addr, host_array as arr, host_view, ptr
 
-LDS_MAX = 148 * 1024     # the largest dynamic LDS block of a workgroup (ORBX_PROJMATCH_LDS lowers it)
-MAX_CAPACITY = 32768
-MAX_LEVELS = 16
 KIND_RELOC, KIND_SIM3 = 0, 1
 ITEM_DTYPE = np.dtype([("frame", "<i4"), ("kind", "<i4"), ("th", "<f4"), ("max_dist", "<f4")])
 POINT_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("angle", "<f4"), ("level", "<i4"), ("point", "<i4"), ("valid", "<i4"), ("pad", "<i4", (2,))])
@@ -32,20 +30,6 @@ def max_dist_reloc(orb_dist: int) -> np.float32:
 def max_dist_sim3(ratio_hamming: float, th_low: int = 50) -> np.float32:
     """bestDist <= TH_LOW * ratioHamming (:523, :636): the float32 product."""
     return np.float32(np.float32(th_low) * np.float32(ratio_hamming))
-
-
-def _up16(n: int) -> int:
-    return (n + 15) & ~15
-
-
-def lds_bytes(capacity: int, mcap: int) -> int:
-    """What the LDS path needs beside the candidate room for frames of this capacity and rows of up to `mcap` points: descriptors, sorted
-    keys, records, cell starts, offsets, the points' results.  A search takes the LDS path when this plus one list of `capacity` candidates
-    is within the handle's limit; the rest of the limit is candidate room (4 bytes a candidate)."""
-    p2 = 2
-    while p2 < capacity:
-        p2 <<= 1
-    return sum(_up16(b) for b in (32 * capacity, 4 * p2, 16 * capacity, 2 * (64 * 48 + 1), 4 * (mcap + 1), 4 * mcap))
 
 
 @dataclass
@@ -83,11 +67,6 @@ class ProjMatchResult:
 
     def __getitem__(self, b: int):
         return int(host_view(self.nmatches[b:b + 1])[0]), host_view(self.kp_match[b])
-
-
-def _table(scale_factors):
-    s = np.ascontiguousarray(scale_factors, np.float32).ravel()
-    return s, s.ctypes.data_as(C.POINTER(C.c_float)), len(s)
 
 
 class ProjMatchBatch(_lib.SideHandle):

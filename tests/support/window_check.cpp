@@ -1,0 +1,73 @@
+// The plain-C++ part of csrc/side/orbx_window_device.h on the host (tests/test_window_core.py): div_rn against the IEEE float division it
+// restates, bit for bit, and layout()'s sizes for the binding's lds_bytes.
+//   div     a in {64, 48} over planted b (zeros, subnormals, FLT_MIN, the floats around the overflow of a / b near 1.9e-37, FLT_MAX,
+//           infinities, a quiet NaN), over EVERY significand of b in two binades and both signs (2^25 divisors per a: whatever rounding case
+//           a division by a normal b can meet is among them), and over 4 million random normal b.
+//           An exact tie and the carry m == 0x1000000 cannot occur in a float division: a tie needs a quotient of 25 significant bits whose
+//           product with b has at most 24, and a quotient below 2 is at most 2 - 2^-23, which is representable.  The sweep holds the
+//           quotients nearest to both.
+//   layout  `layout <cap> <mcap> <fixed>` lines for the LDS path and `lds_max <kLdsMax>`.
+#include <cfloat>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <random>
+
+#include "../../orb_slam3_modified_amd/csrc/side/orbx_window_device.h"
+
+using orbx::side::win::div_rn;
+
+static uint32_t bits(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
+static float from_bits(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
+
+static long g_bad = 0, g_done = 0;
+static void expect(float a, float b, float want, const char* what) {
+  const float got = div_rn(a, b);
+  g_done++;
+  const bool same = std::isnan(want) ? std::isnan(got) : bits(got) == bits(want);
+  if (!same && g_bad++ < 20) printf("MISMATCH %s: %.9g / %.9g (0x%08x) = 0x%08x, want 0x%08x\n", what, a, b, bits(b), bits(got), bits(want));
+}
+static void against_division(float a, float b, const char* what) {
+  volatile float va = a, vb = b;
+  expect(a, b, va / vb, what);
+}
+
+int main() {
+  const float as[2] = {64.0f, 48.0f};
+  for (float a : as) {
+    // zero and subnormal b: the documented infinity, with b's sign
+    for (uint32_t sign : {0u, 0x80000000u})
+      for (uint32_t m : {0u, 1u, 2u, 0x400000u, 0x7FFFFEu, 0x7FFFFFu}) expect(a, from_bits(sign | m), from_bits(sign | 0x7F800000u), "zero or subnormal b");
+    for (float s : {1.0f, -1.0f}) {
+      against_division(a, s * FLT_MIN, "FLT_MIN");
+      against_division(a, s * FLT_MAX, "FLT_MAX");
+      against_division(a, s * INFINITY, "infinite b");
+      expect(a, s * INFINITY, s * 0.0f, "infinite b gives a zero");
+      const uint32_t edge = bits(a / FLT_MAX);                     // the overflow of a / b: 1.88e-37 for 64, 1.41e-37 for 48
+      for (int d = -64; d <= 64; d++) against_division(a, s * from_bits(edge + d), "around the overflow");
+      for (float b : {1.8e-37f, 1.9e-37f, 1.4e-37f, 1.5e-37f}) against_division(a, s * b, "1.9e-37 either side");
+    }
+    const float nan = from_bits(0x7FC00000u);
+    expect(a, nan, nan, "NaN in, NaN out");
+    g_done--;
+    if (bits(div_rn(a, nan)) != 0x7FC00000u) { g_bad++; printf("MISMATCH: the NaN is not handed through\n"); }
+    // every significand, binades of 1 and of 2^-100, both signs
+    for (uint32_t head : {0x3F800000u, 0xBF800000u, 0x0D800000u, 0x8D800000u})
+      for (uint32_t m = 0; m < (1u << 23); m++) against_division(a, from_bits(head | m), "significand sweep");
+    std::mt19937 rng(20260117u);
+    for (int i = 0; i < 2000000; i++) {
+      const uint32_t r = rng(), e = 1u + rng() % 254u;               // a normal b of any binade and sign
+      against_division(a, from_bits((r & 0x807FFFFFu) | e << 23), "random normal b");
+    }
+  }
+  printf("div_rn: %ld comparisons, %ld mismatches\n", g_done, g_bad);
+  const int shapes[5][2] = {{1, 1}, {72, 64}, {1024, 2048}, {5024, 1024}, {32768, 1}};
+  for (const auto& s : shapes) {
+    int p2 = 2;
+    while (p2 < s[0]) p2 <<= 1;
+    printf("layout %d %d %zu\n", s[0], s[1], orbx::side::win::layout(s[0], s[1], p2, true).fixed);
+  }
+  printf("lds_max %d\n", orbx::side::win::kLdsMax);
+  return g_bad ? 1 : 0;
+}

@@ -52,7 +52,7 @@ def test_product_library_keeps_its_abi_and_its_kernels():
     assert build.kernels_hash() == KERNELS_HASH
     assert os.path.dirname(build.LASTMATCH_SOURCE) == "lastmatch" and "orbx_lastmatch.hip" not in os.listdir(build.CSRC)
     src = open(os.path.join(build.CSRC, build.LASTMATCH_SOURCE)).read()
-    assert "side/orbx_handle.h" in src and "side/orbx_pair_device.h" in src and "orbx_internal.h" not in src
+    assert "side/orbx_handle.h" in src and "side/orbx_pair_device.h" in src and "side/orbx_window_device.h" in src and "orbx_internal.h" not in src
 
 
 @pytest.mark.skipif(shutil.which("gcc") is None, reason="gcc not installed")
@@ -86,7 +86,8 @@ def test_python_binding_covers_the_header():
     assert lastmatch.lds_bytes(1024, 1024) + 4 * 16000 <= lastmatch.LDS_MAX < lastmatch.lds_bytes(5024, 1024)
     assert lastmatch.lds_bytes(1024, 2048) == localmatch.lds_bytes(1024, 2048)
     src = open(os.path.join(build.CSRC, build.LASTMATCH_SOURCE)).read()
-    assert "kLdsMax = 148 * 1024" in src and '"ORBX_LASTMATCH_LDS"' in src
+    core = open(os.path.join(build.CSRC, "side", "orbx_window_device.h")).read()      # the three window matchers' shared limit
+    assert "kLdsMax = 148 * 1024" in core and lastmatch.LDS_MAX == 148 * 1024 and '"ORBX_LASTMATCH_LDS"' in src
     # the header states what is out of scope and what is undefined
     text = open(os.path.join(ROOT, "include", HEADER)).read()
     for word in ("two-camera block", "bForward", "non-finite", "asserts", "mo_search_by_projection_last", "ORBX_LASTMATCH_LDS", "ComputeThreeMaxima"):

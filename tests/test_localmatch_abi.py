@@ -50,7 +50,7 @@ def test_product_library_keeps_its_abi_and_its_kernels():
     assert build.kernels_hash() == KERNELS_HASH
     assert os.path.dirname(build.LOCALMATCH_SOURCE) == "localmatch" and "orbx_localmatch.hip" not in os.listdir(build.CSRC)
     src = open(os.path.join(build.CSRC, build.LOCALMATCH_SOURCE)).read()
-    assert "side/orbx_handle.h" in src and "side/orbx_pair_device.h" in src and "orbx_internal.h" not in src
+    assert "side/orbx_handle.h" in src and "side/orbx_pair_device.h" in src and "side/orbx_window_device.h" in src and "orbx_internal.h" not in src
 
 
 @pytest.mark.skipif(shutil.which("gcc") is None, reason="gcc not installed")
@@ -82,7 +82,8 @@ def test_python_binding_covers_the_header():
     # 16 000 candidates, the initialisation extractor's capacity does not fit
     assert localmatch.lds_bytes(1024, 2048) + 4 * 16000 <= localmatch.LDS_MAX < localmatch.lds_bytes(5024, 2048)
     src = open(os.path.join(build.CSRC, build.LOCALMATCH_SOURCE)).read()
-    assert "kLdsMax = 148 * 1024" in src and '"ORBX_LOCALMATCH_LDS"' in src
+    core = open(os.path.join(build.CSRC, "side", "orbx_window_device.h")).read()      # the three window matchers' shared limit
+    assert "kLdsMax = 148 * 1024" in core and localmatch.LDS_MAX == 148 * 1024 and '"ORBX_LOCALMATCH_LDS"' in src
     # the header states what is out of scope and what is undefined
     text = open(os.path.join(ROOT, "include", HEADER)).read()
     for word in ("two-camera block", "isInFrustum", "LastFrame", "non-finite", "mo_search_by_projection", "ORBX_LOCALMATCH_LDS"):

@@ -55,7 +55,7 @@ def test_every_other_library_keeps_its_abi_and_the_product_its_kernels():
     assert build.kernels_hash() == KERNELS_HASH
     assert os.path.dirname(build.PROJMATCH_SOURCE) == "projmatch" and "orbx_projmatch.hip" not in os.listdir(build.CSRC)
     src = open(os.path.join(build.CSRC, build.PROJMATCH_SOURCE)).read()
-    assert "side/orbx_handle.h" in src and "side/orbx_pair_device.h" in src and "orbx_internal.h" not in src
+    assert "side/orbx_handle.h" in src and "side/orbx_pair_device.h" in src and "side/orbx_window_device.h" in src and "orbx_internal.h" not in src
     assert "orbx_lastmatch" not in src.replace("csrc/lastmatch/orbx_lastmatch.hip", "")   # nothing of the last-frame matcher is included or called
 
 
@@ -102,7 +102,8 @@ def test_python_binding_covers_the_header():
     assert projmatch.lds_bytes(1024, 2048) + 4 * 16000 <= projmatch.LDS_MAX < projmatch.lds_bytes(5024, 1024)
     assert projmatch.lds_bytes(1024, 2048) == lastmatch.lds_bytes(1024, 2048)
     src = open(os.path.join(build.CSRC, build.PROJMATCH_SOURCE)).read()
-    assert "kLdsMax = 148 * 1024" in src and '"ORBX_PROJMATCH_LDS"' in src
+    core = open(os.path.join(build.CSRC, "side", "orbx_window_device.h")).read()      # the three window matchers' shared limit
+    assert "kLdsMax = 148 * 1024" in core and projmatch.LDS_MAX == 148 * 1024 and '"ORBX_PROJMATCH_LDS"' in src
     # the header states what is out of scope, what is undefined and the reference's lines
     for word in ("two-camera block", "PredictScale", "non-finite", "asserts", "mo_window_search_grid", "ORBX_PROJMATCH_LDS", "ComputeThreeMaxima",
                  ":1889-2010", ":427-532", ":534-646", "src/KeyFrame.cc:704-748", "at most once", "NaN max_dist", "index [-1]"):
