@@ -30,6 +30,7 @@ PROJMATCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_projmatch.
 PLACE_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_place.so")             # the batched place recognition (include/orbx_place.h)
 PLACEINDEX_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_placeindex.so")   # the same through a device inverted file (include/orbx_placeindex.h)
 FRUSTUM_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_frustum.so")         # the batched Frame::isInFrustum (include/orbx_frustum.h)
+PROJECT_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_project.so")         # the LastFrame, relocalization and Fuse projections (include/orbx_project.h)
 
 ORBX_OK, ORBX_E_INVALID, ORBX_E_EMPTY, ORBX_E_DEVICE, ORBX_E_CAPACITY, ORBX_E_FORMAT = 0, -1, -2, -3, -4, -5
 NUM_KERNELS = 6
@@ -545,10 +546,35 @@ def frustum_lib(path: str = FRUSTUM_LIB_PATH) -> C.CDLL:
     return M
 
 
+def project_lib(path: str = PROJECT_LIB_PATH) -> C.CDLL:
+    """liborbx_project.so.  `_orbx_project_symbols`: every name of include/orbx_project.h, bound here with its signature.  `path`: a timing
+    build of the same source."""
+    vp, i32, f32 = C.c_void_p, C.c_int, C.c_float
+    head, tail = [vp, i32, vp, i32, vp, vp, i32], [i32, i32, vp, vp]   # points, npoints .. mcap; rot_kind .. nvalid
+    last = [vp, vp, i32, vp, i32, vp, vp, i32] + tail                  # with obs
+    sig = {
+        "orbx_project_create": (i32, [C.POINTER(vp), i32]),
+        "orbx_project_destroy": (None, [vp]),
+        "orbx_project_last_error": (C.c_char_p, [vp]),
+        "orbx_project_last_device": (i32, [vp] + last + [vp]),
+        "orbx_project_last": (i32, [vp] + last),
+        "orbx_project_last_reference": (i32, last),
+        "orbx_project_reloc_device": (i32, [vp] + head + [vp, i32] + tail + [vp]),
+        "orbx_project_reloc": (i32, [vp] + head + [vp, i32] + tail),
+        "orbx_project_reloc_reference": (i32, head + [f32, i32, i32] + tail),
+        "orbx_project_fuse_device": (i32, [vp] + head + [vp, vp, i32] + tail + [vp]),
+        "orbx_project_fuse": (i32, [vp] + head + [vp, vp, i32] + tail),
+        "orbx_project_fuse_reference": (i32, head + [f32, vp, i32, i32] + tail),
+    }
+    M = _load_side(path, sig)
+    M._orbx_project_symbols = tuple(sig)
+    return M
+
+
 class SideHandle:
     """A handle of a side library whose entry points are <prefix>_create / _destroy / _last_error (StereoBatch, BowBatch, MatchBatch,
     InitMatchBatch, TriMatchBatch, FuseBatch, DistinctBatch, ScoreBatch, FisheyeBatch, LocalMatchBatch, LastMatchBatch, ProjMatchBatch,
-    PlaceBatch, PlaceIndex, FrustumBatch)."""
+    PlaceBatch, PlaceIndex, FrustumBatch, ProjectBatch)."""
 
     def __init__(self, library: C.CDLL, prefix: str, *create_args):
         self._L, self._prefix, self._h = library, prefix, C.c_void_p(0)

@@ -22,6 +22,8 @@ LIBS is the one place that knows them, one record per library; what is stale, wh
   liborbx_placeindex.so the same candidates through a device inverted file that grows (include/orbx_placeindex.h); takes nothing from it
   liborbx_frustum.so    the batched Frame::isInFrustum + PredictScale, written as liborbx_localmatch.so's point rows (include/orbx_frustum.h);
                         takes nothing from the product
+  liborbx_project.so    the Sophus Tcw * x projection fronts of the LastFrame, relocalization and Fuse matchers, written as those
+                        matchers' rows (include/orbx_project.h); takes nothing from the product
 The libraries beside the product link liborbx.so and use its ABI (and orbx_internal.h where they read a context's buffers).  Their sources sit
 in subdirectories of csrc/, outside kernels_hash(): the committed counter files measure the product's kernels, which they do not change.
 A new one is one more record ("Adding a side library")."""
@@ -72,6 +74,8 @@ PLACEINDEX_OUT = os.path.join(os.path.dirname(OUT), "liborbx_placeindex.so")
 PLACEINDEX_SOURCE = os.path.join("placeindex", "orbx_placeindex.hip")
 FRUSTUM_OUT = os.path.join(os.path.dirname(OUT), "liborbx_frustum.so")
 FRUSTUM_SOURCE = os.path.join("frustum", "orbx_frustum.hip")
+PROJECT_OUT = os.path.join(os.path.dirname(OUT), "liborbx_project.so")
+PROJECT_SOURCE = os.path.join("project", "orbx_project.hip")
 
 
 class Lib(NamedTuple):
@@ -99,10 +103,11 @@ LIBS = (Lib(OUT, tuple(SOURCES)),
         Lib(PROJMATCH_OUT, (PROJMATCH_SOURCE,), hidden=True, product=True, deps=WINDOW_CORE),
         Lib(PLACE_OUT, (PLACE_SOURCE,), hidden=True, deps=(PLACE_KERNELS,)),
         Lib(PLACEINDEX_OUT, (PLACEINDEX_SOURCE,), hidden=True, deps=(PLACE_KERNELS,)),
-        Lib(FRUSTUM_OUT, (FRUSTUM_SOURCE,), hidden=True))
+        Lib(FRUSTUM_OUT, (FRUSTUM_SOURCE,), hidden=True),
+        Lib(PROJECT_OUT, (PROJECT_SOURCE,), hidden=True))
 HEADERS = ("orbx.h", "orbx_debug.h", "orbx_train.h", "orbx_stereo.h", "orbx_bow.h", "orbx_match.h", "orbx_initmatch.h", "orbx_trimatch.h",
            "orbx_fuse.h", "orbx_mpdesc.h", "orbx_score.h", "orbx_fisheye.h", "orbx_localmatch.h", "orbx_lastmatch.h",
-           "orbx_projmatch.h", "orbx_place.h", "orbx_placeindex.h", "orbx_frustum.h")
+           "orbx_projmatch.h", "orbx_place.h", "orbx_placeindex.h", "orbx_frustum.h", "orbx_project.h")
 # -ffp-contract=off: the float paths (fastAtan2 polynomial, BRIEF rotation) must not be fused into FMAs,
 # the CPU reference evaluates them as separate IEEE operations (DESIGN.md "bit-exactness").
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall",

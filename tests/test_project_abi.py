@@ -1,0 +1,205 @@
+"""include/orbx_project.h <-> liborbx_project.so: the projection fronts of the LastFrame, relocalization and Fuse matchers are a library
+of their own beside the product (CPU-only checks)."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import abi_util
+from tests.abi_util import declared as _declared, exported as _exported
+
+ROOT = abi_util.ROOT
+KERNELS_HASH = "cfa5f580d25d496f"   # the product's kernel sources: this library changes none of them
+HEADER = "orbx_project.h"
+NAMES = ("create", "destroy", "last_error") + tuple(e + f for e in ("last", "reloc", "fuse") for f in ("_device", "", "_reference"))
+
+
+def _fields(name: str) -> list:
+    """(field, array length or 1) of `typedef struct <name> { ... }` in the header, in order."""
+    h = open(os.path.join(ROOT, "include", HEADER)).read()
+    body = re.sub(r"/\*.*?\*/", "", h[h.index("typedef struct %s {" % name):h.index("} %s;" % name)], flags=re.S)
+    return [(n, int(k or 1)) for decl in re.findall(r"(?:float|int32_t)\s+([^;]+);", body)
+            for n, k in re.findall(r"(\w+)(?:\[(\d+)\])?\s*(?:,|$)", decl.strip())]
+
+
+def test_build_produces_the_project_library():
+    from orb_slam3_modified_amd import _lib, build
+    build.build()
+    assert os.path.isfile(build.PROJECT_OUT) and build.PROJECT_OUT == _lib.PROJECT_LIB_PATH
+    assert os.path.dirname(build.PROJECT_OUT) == os.path.dirname(_lib.LIB_PATH) == os.path.join(ROOT, "orb_slam3_modified_amd")
+    assert os.path.basename(build.PROJECT_OUT) == "liborbx_project.so" and HEADER in build.HEADERS
+    rec = [l for l in build.LIBS if l.out == build.PROJECT_OUT]
+    assert len(rec) == 1 and rec[0].sources == (build.PROJECT_SOURCE,) and rec[0].hidden and not rec[0].product
+    assert "-ffp-contract=off" in build.FLAGS                      # no product and sum, and no product and difference, is fused
+    assert not [f for f in build.FLAGS if "fast" in f or "correctly-rounded" in f or "unsafe" in f or "denormal" in f], build.FLAGS
+
+
+def test_project_library_exports_exactly_its_header():
+    from orb_slam3_modified_amd import _lib, build
+    build.build()
+    names = _declared(HEADER)
+    assert names == sorted("orbx_project_" + n for n in NAMES), names
+    exported = _exported(_lib.PROJECT_LIB_PATH)
+    assert {e for e in exported if e.startswith("orbx_")} == set(names)
+    assert not [e for e in exported if not e.startswith("orbx_project_") and not e.startswith("_")], sorted(exported)[:10]   # -fvisibility=hidden
+    needed = subprocess.check_output(["readelf", "-d", _lib.PROJECT_LIB_PATH]).decode()
+    assert "liborbx" not in needed                                 # it takes nothing from the product or from the matchers it feeds
+
+
+def test_every_other_library_keeps_its_abi_and_the_product_its_kernels():
+    from orb_slam3_modified_amd import build
+    build.build()
+    names = set(_declared(HEADER))
+    others = [l.out for l in build.LIBS if l.out != build.PROJECT_OUT]
+    assert len(others) == len(build.LIBS) - 1
+    for other in others:
+        assert not names & _exported(other), other
+    for header in build.HEADERS:
+        if header != HEADER:
+            assert not names & set(_declared(header)), header
+    assert len(_declared("orbx.h")) == 100 and build.kernels_hash() == KERNELS_HASH
+    assert len(_declared("orbx_frustum.h")) == 7 and len(_declared("orbx_lastmatch.h")) == 5 and len(_declared("orbx_projmatch.h")) == 5
+    assert os.path.dirname(build.PROJECT_SOURCE) == "project" and "orbx_project.hip" not in os.listdir(build.CSRC)
+    src = open(os.path.join(build.CSRC, build.PROJECT_SOURCE)).read()
+    assert "side/orbx_handle.h" in src and "orbx_internal.h" not in src
+    code = re.sub(r"//.*", "", src)
+    assert "asm" not in code and not re.search(r"atomic\w*\s*\(\s*\(?\s*(float|double)", code)
+    # one statement of the specification: the kernel and the four option pairs of the host twin; no log on the device; no bisection here
+    assert code.count("emit_one<") == 5 and "log(" not in code[code.index("__global__"):] and "level_thresholds" not in code
+
+
+@pytest.mark.skipif(shutil.which("gcc") is None, reason="gcc not installed")
+def test_the_header_compiles_as_c(tmp_path):
+    src = tmp_path / "use.c"
+    src.write_text('#include "orbx_project.h"\nint main(void) { orbx_project_item i; orbx_project_slot s; return (int)sizeof(i) + (int)sizeof(s); }\n'
+                   'typedef char item_is_128[sizeof(orbx_project_item) == 128 ? 1 : -1];\n'
+                   'typedef char slot_is_16[sizeof(orbx_project_slot) == 16 ? 1 : -1];\n'
+                   'typedef char point_is_48[sizeof(orbx_frustum_point) == 48 ? 1 : -1];\n'
+                   'typedef char rows_are_32[sizeof(orbx_lastmatch_point) == 32 && sizeof(orbx_projmatch_point) == 32 '
+                   '&& sizeof(orbx_fuse_query) == 32 ? 1 : -1];\n')
+    p = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), "-c", str(src), "-o",
+                        str(tmp_path / "use.o")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert p.returncode == 0, p.stdout[-2000:]
+
+
+def test_python_binding_covers_the_header():
+    from orb_slam3_modified_amd import _lib, build
+    build.build()
+    M = _lib.project_lib()
+    assert set(M._orbx_project_symbols) == set(_declared(HEADER))
+    from orb_slam3_modified_amd import project
+    assert issubclass(project.ProjectBatch, _lib.SideHandle)
+    for m in ("last", "reloc", "fuse", "last_host", "reloc_host", "fuse_host"):
+        assert callable(getattr(project.ProjectBatch, m))
+    assert callable(project.reference_last) and callable(project.reference_reloc) and callable(project.reference_fuse)
+    # the records the binding passes are the header's: the same fields, in order and size
+    for struct, dtype, size in (("orbx_project_item", project.ITEM_DTYPE, 128), ("orbx_project_slot", project.SLOT_DTYPE, 16)):
+        assert _fields(struct) == [(n, int(np.prod(dtype[n].shape, dtype=int))) for n in dtype.names] and dtype.itemsize == size, _fields(struct)
+    assert project.ITEM_DTYPE.fields["q"][1] == 15 * 4 and project.ITEM_DTYPE.fields["th"][1] == 28 * 4
+    text = open(os.path.join(ROOT, "include", HEADER)).read()
+    for name, value in (("ROT_MATRIX", 0), ("ROT_QUAT", 1)):
+        assert re.search(r"#define ORBX_PROJECT_%s %d\b" % (name, value), text) and getattr(project, name) == value
+    # the header states what is out of scope and what is not settled
+    for word in ("Sim3", "SearchBySim3", ":427", ":534", ":1340", "bRight", "two-camera", "KannalaBrandt8", "bForward", "bBackward", "side effects",
+                 "a real Eigen", "has not been settled", "never inverts", "half-open", "no depth test", "equals the float quotient",
+                 "strictly increasing"):
+        assert word in text, word
+
+
+def test_bad_arguments_are_rejected_without_a_device():
+    """Argument checks that come before any device call, all forms; the host twins need no device at all."""
+    from orb_slam3_modified_amd import _lib, project
+    M = _lib.project_lib()
+    h = C.c_void_p(0)
+    assert M.orbx_project_create(None, 0) == _lib.ORBX_E_INVALID
+    assert b"null" in M.orbx_project_last_error(None)
+    assert M.orbx_project_create(C.byref(h), -1) == _lib.ORBX_E_INVALID and not h.value
+    assert b"device" in M.orbx_project_last_error(None)
+    M.orbx_project_destroy(None)
+    head = (None, 1, None, 1, None, None, 8)
+    assert M.orbx_project_last_device(None, None, None, 1, None, 1, None, None, 8, 0, 0, None, None, None) == _lib.ORBX_E_INVALID
+    assert M.orbx_project_last(None, None, None, 1, None, 1, None, None, 8, 0, 0, None, None) == _lib.ORBX_E_INVALID
+    assert M.orbx_project_reloc_device(None, *head, None, 8, 0, 0, None, None, None) == _lib.ORBX_E_INVALID
+    assert M.orbx_project_reloc(None, *head, None, 8, 0, 0, None, None) == _lib.ORBX_E_INVALID
+    assert M.orbx_project_fuse_device(None, *head, None, None, 8, 0, 0, None, None, None) == _lib.ORBX_E_INVALID
+    assert M.orbx_project_fuse(None, *head, None, None, 8, 0, 0, None, None) == _lib.ORBX_E_INVALID
+    # the host twins run the same checks as the device forms (one function) and report the reason
+    pts, obs = np.zeros(4, project.TABLE_DTYPE), np.zeros(4, np.int32)
+    items, slots, nslots = np.zeros(2, project.ITEM_DTYPE), np.zeros((2, 8), project.SLOT_DTYPE), np.zeros(2, np.int32)
+    idx, sf = np.zeros((2, 8), np.int32), np.ones(8, np.float32)
+    out, nvalid = np.zeros((2, 8, 32), np.uint8), np.zeros(2, np.int32)
+    p = _lib.ptr
+
+    def call(kind, points=pts, obs_=obs, npoints=4, items_=items, nitems=2, slots_=None, nslots_=nslots, mcap=8, lsf=0.18, sf_=sf, nlevels=8,
+             log=0, rot=0, order=0, out_=out, nvalid_=nvalid):
+        front = (p(points), npoints, p(items_), nitems, p((idx if kind == "fuse" else slots) if slots_ is None else slots_ or None), p(nslots_), mcap)
+        tail = (rot, order, p(out_), p(nvalid_))
+        if kind == "last":
+            return M.orbx_project_last_reference(front[0], p(obs_), *front[1:], *tail)
+        if kind == "reloc":
+            return M.orbx_project_reloc_reference(*front, lsf, nlevels, log, *tail)
+        return M.orbx_project_fuse_reference(*front, lsf, p(sf_), nlevels, log, *tail)
+
+    shared = ((dict(points=None), b"null"), (dict(items_=None), b"null"), (dict(slots_=0), b"null"), (dict(nslots_=None), b"null"),
+              (dict(out_=None), b"null"), (dict(nvalid_=None), b"null"), (dict(npoints=0), b"at least 1"), (dict(nitems=0), b"at least 1"),
+              (dict(mcap=0), b"at least 1"), (dict(rot=2), b"rot_kind"), (dict(order=2), b"sum_order"), (dict(order=-1), b"sum_order"),
+              (dict(nitems=1 << 20, mcap=1 << 12), b"INT_MAX"))
+    levels = ((dict(nlevels=0), b"nlevels"), (dict(nlevels=17), b"nlevels"), (dict(log=-1), b"log_kind"), (dict(log=2), b"log_kind"),
+              (dict(lsf=float("nan")), b"finite"), (dict(lsf=0.0), b"finite"), (dict(lsf=-0.1), b"finite"), (dict(lsf=float("inf")), b"finite"))
+    for kind, cases in (("last", shared + ((dict(obs_=None), b"null"),)), ("reloc", shared + levels),
+                        ("fuse", shared + levels + ((dict(sf_=None), b"scale_factors"),))):
+        assert call(kind) == _lib.ORBX_OK and list(nvalid) == [0, 0], kind
+        for kw, word in cases:
+            assert call(kind, **kw) == _lib.ORBX_E_INVALID, (kind, kw)
+            assert word in M.orbx_project_last_error(None), (kind, kw, M.orbx_project_last_error(None))
+    src = open(os.path.join(ROOT, "orb_slam3_modified_amd", "csrc", "project", "orbx_project.hip")).read()
+    assert src.count("call_problem(") == 10 and "16-byte aligned" in src and "same_device(" in src   # what only the device forms can check
+    assert src.count("thresholds_problem(") == 5                  # the definition and the four forms that take thresholds
+
+
+def test_bad_thresholds_are_rejected_before_any_device_call():
+    """The thresholds are checked with the other arguments, before anything is staged or launched.  No handle can be made without a
+    device, so this reads the order off the source; tests/test_gpu_project.py makes the calls and reads the reasons."""
+    src = open(os.path.join(ROOT, "orb_slam3_modified_amd", "csrc", "project", "orbx_project.hip")).read()
+    for form in ("orbx_project_reloc_device", "orbx_project_reloc", "orbx_project_fuse_device", "orbx_project_fuse"):
+        body = src[src.index("int %s(" % form):]
+        body = body[:body.index("\n}\n")]
+        assert body.index("thresholds_problem(") < body.index("return project_"), form       # before the staging and the launch
+    text = src[src.index("const char* thresholds_problem("):]
+    text = text[:text.index("\n}\n")]
+    for reason in ("null thresholds", "finite and positive", "strictly increasing", "levels_problem"):
+        assert reason in text, reason
+    assert "isfinite" in text and "T[n] > T[n - 1]" in text and "T[n] > 0.0f" in text
+
+
+@abi_util.needs_hipcc
+def test_project_kernels_compile_without_scratch():
+    from orb_slam3_modified_amd.build import PROJECT_SOURCE
+    scratch = abi_util.kernel_scratch(PROJECT_SOURCE, hidden=True)
+    assert len([n for n in scratch if "k_project" in n]) == 13 and len(scratch) == 13   # the check; emitter x rot_kind x sum_order
+    assert all(v == 0 for v in scratch.values()), scratch
+
+
+@abi_util.needs_hipcc
+def test_the_emitters_read_their_item_through_scalar_loads_and_write_whole_rows():
+    """The item's constants, the thresholds and the scale factors are workgroup-uniform: scalar loads, not a load per lane.  A lane
+    writes its row as two 16-byte stores; one integer atomic per wave; nothing is a flat access.  That no product is fused with the sum
+    or the difference after it is the GPU test's to show, bit for bit."""
+    from orb_slam3_modified_amd.build import PROJECT_SOURCE
+    asm = abi_util.device_asm(PROJECT_SOURCE, hidden=True)
+    assert "flat_load" not in asm and "flat_store" not in asm and "flat_atomic" not in asm
+    kernels = re.findall(r"^\s*\.amdhsa_kernel\s+(\S*k_project\S+)", asm, flags=re.M)
+    emitters = [k for k in kernels if "check" not in k]
+    assert len(emitters) == 12
+    for name in emitters:
+        k = asm[asm.index(name + ":"):]
+        k = k[:k.index("s_endpgm")]
+        assert len(re.findall(r"global_store_dwordx4", k)) == 2 and not re.findall(r"\bglobal_store_dword\b", k), name
+        assert len(re.findall(r"global_atomic_add\b", k)) == 1 and "global_atomic_add_f32" not in k, name
+        assert "s_bcnt1_i32_b64" in k, name                                     # the ballot's popcount
+        scalar_dwords = sum({"": 1, "x2": 2, "x4": 4, "x8": 8, "x16": 16}[w] for w in re.findall(r"s_load_dword(x\d+)?\b", k))
+        assert scalar_dwords >= 20, (name, scalar_dwords)                       # the item
