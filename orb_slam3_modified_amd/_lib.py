@@ -31,6 +31,7 @@ PLACE_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_place.so")    
 PLACEINDEX_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_placeindex.so")   # the same through a device inverted file (include/orbx_placeindex.h)
 FRUSTUM_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_frustum.so")         # the batched Frame::isInFrustum (include/orbx_frustum.h)
 PROJECT_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_project.so")         # the LastFrame, relocalization and Fuse projections (include/orbx_project.h)
+SIM3_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_sim3.so")               # LoopClosing's Sim3 projections and agreement pass (include/orbx_sim3.h)
 
 ORBX_OK, ORBX_E_INVALID, ORBX_E_EMPTY, ORBX_E_DEVICE, ORBX_E_CAPACITY, ORBX_E_FORMAT = 0, -1, -2, -3, -4, -5
 NUM_KERNELS = 6
@@ -571,10 +572,39 @@ def project_lib(path: str = PROJECT_LIB_PATH) -> C.CDLL:
     return M
 
 
+def sim3_lib(path: str = SIM3_LIB_PATH) -> C.CDLL:
+    """liborbx_sim3.so.  `_orbx_sim3_symbols`: every name of include/orbx_sim3.h, bound here with its signature.  `path`: a timing build of
+    the same source."""
+    vp, i32, f32 = C.c_void_p, C.c_int, C.c_float
+    head, tail = [vp, i32, vp, i32, vp, vp, i32], [i32, i32, vp, vp]   # points, npoints .. mcap; rot_kind, sum_order, out, nvalid
+    stail = [i32, i32, i32, vp, vp]                                    # search: with sim_kind
+    agree = [vp] * 8 + [i32, i32, i32, vp, vp]
+    sig = {
+        "orbx_sim3_create": (i32, [C.POINTER(vp), i32]),
+        "orbx_sim3_destroy": (None, [vp]),
+        "orbx_sim3_last_error": (C.c_char_p, [vp]),
+        "orbx_sim3_proj_device": (i32, [vp] + head + [vp, i32, i32] + tail + [vp]),   # thresholds, nlevels, proj_kind
+        "orbx_sim3_proj": (i32, [vp] + head + [vp, i32, i32] + tail),
+        "orbx_sim3_proj_reference": (i32, head + [f32, i32, i32, i32] + tail),
+        "orbx_sim3_fuse_device": (i32, [vp] + head + [vp, vp, i32] + tail + [vp]),
+        "orbx_sim3_fuse": (i32, [vp] + head + [vp, vp, i32] + tail),
+        "orbx_sim3_fuse_reference": (i32, head + [f32, vp, i32, i32] + tail),
+        "orbx_sim3_search_device": (i32, [vp] + head + [vp, vp, i32] + stail + [vp]),
+        "orbx_sim3_search": (i32, [vp] + head + [vp, vp, i32] + stail),
+        "orbx_sim3_search_reference": (i32, head + [f32, vp, i32, i32] + stail),
+        "orbx_sim3_agree_device": (i32, [vp] + agree + [vp]),
+        "orbx_sim3_agree": (i32, [vp] + agree),
+        "orbx_sim3_agree_reference": (i32, agree),
+    }
+    M = _load_side(path, sig)
+    M._orbx_sim3_symbols = tuple(sig)
+    return M
+
+
 class SideHandle:
     """A handle of a side library whose entry points are <prefix>_create / _destroy / _last_error (StereoBatch, BowBatch, MatchBatch,
     InitMatchBatch, TriMatchBatch, FuseBatch, DistinctBatch, ScoreBatch, FisheyeBatch, LocalMatchBatch, LastMatchBatch, ProjMatchBatch,
-    PlaceBatch, PlaceIndex, FrustumBatch, ProjectBatch)."""
+    PlaceBatch, PlaceIndex, FrustumBatch, ProjectBatch, Sim3Batch)."""
 
     def __init__(self, library: C.CDLL, prefix: str, *create_args):
         self._L, self._prefix, self._h = library, prefix, C.c_void_p(0)
