@@ -80,6 +80,7 @@ PROJECT_OUT = os.path.join(os.path.dirname(OUT), "liborbx_project.so")
 PROJECT_SOURCE = os.path.join("project", "orbx_project.hip")
 SIM3_OUT = os.path.join(os.path.dirname(OUT), "liborbx_sim3.so")
 SIM3_SOURCE = os.path.join("sim3", "orbx_sim3.hip")
+FRONT_CORE = (os.path.join("side", "orbx_front_device.h"), os.path.join("side", "orbx_front_host.h"))   # what the three projection fronts share
 
 
 class Lib(NamedTuple):
@@ -107,9 +108,9 @@ LIBS = (Lib(OUT, tuple(SOURCES)),
         Lib(PROJMATCH_OUT, (PROJMATCH_SOURCE,), hidden=True, product=True, deps=WINDOW_CORE),
         Lib(PLACE_OUT, (PLACE_SOURCE,), hidden=True, deps=(PLACE_KERNELS,)),
         Lib(PLACEINDEX_OUT, (PLACEINDEX_SOURCE,), hidden=True, deps=(PLACE_KERNELS,)),
-        Lib(FRUSTUM_OUT, (FRUSTUM_SOURCE,), hidden=True),
-        Lib(PROJECT_OUT, (PROJECT_SOURCE,), hidden=True),
-        Lib(SIM3_OUT, (SIM3_SOURCE,), hidden=True))
+        Lib(FRUSTUM_OUT, (FRUSTUM_SOURCE,), hidden=True, deps=FRONT_CORE),
+        Lib(PROJECT_OUT, (PROJECT_SOURCE,), hidden=True, deps=FRONT_CORE),
+        Lib(SIM3_OUT, (SIM3_SOURCE,), hidden=True, deps=FRONT_CORE))
 HEADERS = ("orbx.h", "orbx_debug.h", "orbx_train.h", "orbx_stereo.h", "orbx_bow.h", "orbx_match.h", "orbx_initmatch.h", "orbx_trimatch.h",
            "orbx_fuse.h", "orbx_mpdesc.h", "orbx_score.h", "orbx_fisheye.h", "orbx_localmatch.h", "orbx_lastmatch.h",
            "orbx_projmatch.h", "orbx_place.h", "orbx_placeindex.h", "orbx_frustum.h", "orbx_project.h", "orbx_sim3.h")

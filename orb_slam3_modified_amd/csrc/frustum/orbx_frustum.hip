@@ -2,7 +2,9 @@
 // HBM, written as the orbx_localmatch_point rows the batched SearchLocalPoints reads.
 //
 // project_one<kTree> is the specification, stated once for the host and the device; what differs is where the level comes from: the host
-// twin calls libm's log (HostLevel), the kernel counts the thresholds the host bisected through that same libm (DeviceLevel).
+// twin calls libm's log (HostLevel), the kernel counts the thresholds the host bisected through that same libm (DeviceLevel).  Both, the
+// bisection, sum3, the table's readers, the check and the lanes' bookkeeping are the projection-front core's (../side/orbx_front_device.h,
+// orbx_front_host.h), shared with liborbx_project.so and liborbx_sim3.so.
 //
 // k_frustum_check      one workgroup per item: nmp and every index of the row's first nmp against npoints, before any of them addresses the
 //                      table; d_ntomatch[b] = -1 (malformed) or 0.
@@ -22,16 +24,13 @@
 #include <string>
 
 #include "../side/orbx_handle.h"
+#include "../side/orbx_front_host.h"
 #include "../../../include/orbx_frustum.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kMaxT = ORBX_FRUSTUM_MAX_LEVELS - 1;
-static_assert(sizeof(orbx_frustum_point) == 48 && sizeof(orbx_frustum_item) == 112 && sizeof(orbx_localmatch_point) == 32, "record sizes");
-
-template <bool kTree>
-__host__ __device__ inline float sum3(float a, float b, float c) { return kTree ? a + (b + c) : (a + b) + c; }
+using namespace orbx::side::front;
+static_assert(sizeof(orbx_frustum_item) == 112 && sizeof(orbx_localmatch_point) == 32, "record sizes");
 
 // Steps 1 .. 11 of the header for one slot below nmp; idx < npoints is the caller's.  Returns whether the slot counts in ntomatch.
 template <bool kTree, class Points, class Level>
@@ -68,70 +67,12 @@ __host__ __device__ inline bool project_one(const orbx_frustum_item& c, const Po
   return true;
 }
 
-// ---------------------------------------------------------------------------------------------------------------- the level on the host
-// ceil(log(ratio) / mfLogScaleFactor) as the C++ expression evaluates under each overload of log, before the conversion to int
-inline double level_quotient(float ratio, float lsf, int log_kind) {
-  if (log_kind == ORBX_FRUSTUM_LOG_FLOAT) {
-    const float q = std::log(ratio) / lsf;          // std::log(float): libm's logf, a float division
-    return std::ceil((double)q);
-  }
-  return std::ceil(::log((double)ratio) / (double)lsf);   // ::log(double), the float divisor promoted
-}
-// int nScale = <quotient>, then the clamp.  Outside the range of int (NaN included) x86's conversion gives INT_MIN, which the clamp raises to 0
-inline int level_clamp(double q, int nlevels) {
-  if (!(q >= -2147483648.0 && q < 2147483648.0)) return 0;
-  const int n = (int)q;
-  return n < 0 ? 0 : n >= nlevels ? nlevels - 1 : n;
-}
-struct HostLevel {
-  float lsf; int nlevels, log_kind;
-  int operator()(float ratio) const { return level_clamp(level_quotient(ratio, lsf, log_kind), nlevels); }
-};
-
-inline float from_bits(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
-
-// T[n], n in 0 .. nlevels-2: the largest positive finite float whose level is <= n.  Why it cannot be had, or nullptr.
-const char* level_thresholds(float lsf, int nlevels, int log_kind, float* T, std::string* why) {
-  const HostLevel level = {lsf, nlevels, log_kind};
-  constexpr uint32_t kLo = 1u, kHi = 0x7F7FFFFFu;   // the smallest subnormal, FLT_MAX
-  // the quotient stays within int over all positive floats, so the x86 rule never cuts into the step
-  for (uint32_t e : {kLo, kHi}) {
-    const double q = level_quotient(from_bits(e), lsf, log_kind);
-    if (!(q >= -2147483648.0 && q < 2147483648.0)) return "log_scale_factor is too small: the level quotient leaves the range of int";
-  }
-  if (level(from_bits(kLo)) != 0) return "the smallest positive ratio does not have level 0";
-  for (int n = 0; n + 1 < nlevels; n++) {
-    uint32_t lo = kLo, hi = kHi;                   // level(lo) <= n throughout
-    if (level(from_bits(hi)) <= n) lo = hi;        // no finite ratio reaches level n + 1
-    while (hi - lo > 1 && lo != hi) {
-      const uint32_t mid = lo + (hi - lo) / 2;
-      if (level(from_bits(mid)) <= n) lo = mid; else hi = mid;
-    }
-    T[n] = from_bits(lo);
-    // the step itself: 4096 floats on either side
-    for (uint32_t k = 0; k < 4096; k++) {
-      const bool below_ok = lo < kLo + k || level(from_bits(lo - k)) <= n;
-      const bool above_ok = lo + 1 + k > kHi || level(from_bits(lo + 1 + k)) > n;
-      if (!below_ok || !above_ok) {
-        char buf[160];
-        snprintf(buf, sizeof buf, "the level is not a clean step of ratio around %a (level %d, log_scale_factor %a, log_kind %d)", (double)T[n], n,
-                 (double)lsf, log_kind);
-        *why = buf;
-        return why->c_str();
-      }
-    }
-    if (n > 0 && T[n] < T[n - 1]) return "the thresholds do not ascend";
-  }
-  return nullptr;
-}
-
 const char* options_problem(int nlevels, int sum_order, int log_kind) {
-  if (nlevels < 1 || nlevels > ORBX_FRUSTUM_MAX_LEVELS) return "nlevels must be in 1 .. 16";
-  if (sum_order != ORBX_FRUSTUM_SUM_LTR && sum_order != ORBX_FRUSTUM_SUM_TREE) return "unknown sum_order";
+  if (const char* e = levels_problem(nlevels)) return e;
+  if (const char* e = sum_problem(sum_order)) return e;
   if (log_kind != ORBX_FRUSTUM_LOG_DOUBLE && log_kind != ORBX_FRUSTUM_LOG_FLOAT) return "unknown log_kind";
   return nullptr;
 }
-inline bool usable_lsf(float lsf) { return std::isfinite(lsf) && lsf > 0.0f; }
 
 // ---------------------------------------------------------------------------------------------------------------------------- the kernels
 struct Args {
@@ -143,59 +84,20 @@ struct Args {
   float T[kMaxT];        // +inf beyond nlevels - 2
 };
 
-struct DeviceLevel {
-  const float* T;
-  __device__ int operator()(float ratio) const {
-    if (!(ratio > 0.0f) || ratio == INFINITY) return 0;
-    int l = 0;
-#pragma unroll
-    for (int n = 0; n < kMaxT; n++) l += ratio > T[n] ? 1 : 0;
-    return l;
-  }
-};
-struct DevicePoints {
-  const float4* t;
-  __device__ orbx_frustum_point operator()(int idx) const {
-    const float4 a = t[3 * (size_t)idx], b = t[3 * (size_t)idx + 1], c = t[3 * (size_t)idx + 2];
-    return {{a.x, a.y, a.z}, a.w, {b.x, b.y, b.z}, b.w, c.x, {0.0f, 0.0f, 0.0f}};
-  }
-};
-struct HostPoints {
-  const orbx_frustum_point* t;
-  const orbx_frustum_point& operator()(int idx) const { return t[idx]; }
-};
-
 __global__ __launch_bounds__(kThreads) void k_frustum_check(Args g) {
   const int b = blockIdx.x;
-  const int nmp = g.nmp[b];
-  int bad = g.all_bad || nmp < 0 || nmp > g.mcap;
-  if (!bad) {
-    const int32_t* row = g.idx + (size_t)b * g.mcap;
-    for (int j = threadIdx.x; j < nmp; j += kThreads) bad |= row[j] >= g.npoints;
-  }
-  bad = __syncthreads_or(bad);
-  if (threadIdx.x == 0) g.ntomatch[b] = bad ? -1 : 0;
+  check_item(g.idx + (size_t)b * g.mcap, 1, g.nmp[b], g.mcap, g.npoints, g.all_bad, g.ntomatch + b);
 }
 
 template <bool kTree>
 __global__ __launch_bounds__(kThreads) void k_frustum(Args g) {
-  const int b = (int)(blockIdx.x / (unsigned)g.chunks);
-  const int j = (int)(blockIdx.x - (unsigned)b * (unsigned)g.chunks) * kThreads + (int)threadIdx.x;
-  // -1 stays -1: a malformed item adds nothing; a sound one only grows from 0
-  const bool bad = __hip_atomic_load(g.ntomatch + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < 0;
-  const int nmp = bad ? 0 : g.nmp[b];
+  const Lane l = lane_of(g.idx, 1, g.nmp, g.ntomatch, g.mcap, g.chunks);
+  orbx_localmatch_point r = {0.0f, 0.0f, 0.0f, 0.0f, 0, 0, 0, 0};
+  float depth = 0.0f;
   bool counts = false;
-  if (j < g.mcap) {
-    const size_t slot = (size_t)b * g.mcap + j;
-    orbx_localmatch_point r = {0.0f, 0.0f, 0.0f, 0.0f, 0, 0, 0, 0};
-    float depth = 0.0f;
-    if (j < nmp) counts = project_one<kTree>(g.items[b], DevicePoints{g.points}, g.obs, g.idx[slot], g.cos_limit, DeviceLevel{g.T}, &r, &depth);
-    g.mp[2 * slot] = make_float4(r.proj_x, r.proj_y, r.proj_xr, r.view_cos);
-    g.mp[2 * slot + 1] = make_float4(__int_as_float(r.level), __int_as_float(r.obs), __int_as_float(r.point), __int_as_float(r.in_view));
-    if (g.depth) g.depth[slot] = depth;
-  }
-  const int n = __popcll(__ballot(counts));
-  if (n > 0 && (threadIdx.x & 63) == 0) atomicAdd(g.ntomatch + b, n);
+  if (l.live) counts = project_one<kTree>(g.items[l.b], DevicePoints{g.points}, g.obs, l.point, g.cos_limit, DeviceLevel{g.T, nullptr}, &r, &depth);
+  finish(l, g.mp, g.ntomatch, Row{{fw(r.proj_x), fw(r.proj_y), fw(r.proj_xr), fw(r.view_cos), iw(r.level), iw(r.obs), iw(r.point), iw(r.in_view)}}, counts,
+         g.depth, depth);
 }
 
 }  // namespace
@@ -214,13 +116,10 @@ using namespace orbx::side;
 // what every form checks before anything is computed, copied or launched; the reason, or nullptr
 const char* call_problem(const void* points, const void* obs, int npoints, const void* items, int nitems, const void* idx, const void* nmp, int mcap,
                          int nlevels, float cos_limit, int sum_order, int log_kind, const void* mp, const void* ntomatch) {
-  if (!points || !obs || !items || !idx || !nmp) return "null points, obs, items, idx or nmp";
-  if (!mp || !ntomatch) return "null mp or ntomatch";
-  if (npoints < 1 || nitems < 1 || mcap < 1) return "npoints, nitems and mcap must be at least 1";
-  if (const char* e = options_problem(nlevels, sum_order, log_kind)) return e;
-  if (cos_limit != cos_limit) return "cos_limit is NaN";
-  if ((long long)nitems * mcap > (long long)INT_MAX) return "nitems * mcap exceeds INT_MAX";
-  return nullptr;
+  const char* missing = !points || !obs || !items || !idx || !nmp ? "null points, obs, items, idx or nmp" : !mp || !ntomatch ? "null mp or ntomatch" : nullptr;
+  const char* own = options_problem(nlevels, sum_order, log_kind);
+  if (!own && cos_limit != cos_limit) own = "cos_limit is NaN";
+  return common_problem(missing, npoints, nitems, mcap, own);
 }
 
 }  // namespace
@@ -256,9 +155,9 @@ int orbx_frustum_project_device(orbx_frustum* f, const orbx_frustum_point* d_poi
   if (const char* e = call_problem(d_points, d_obs, npoints, d_items, nitems, d_idx, d_nmp, mcap, nlevels, cos_limit, sum_order, log_kind, d_mp,
                                    d_ntomatch))
     return fail(f, ORBX_E_INVALID, who + e);
-  if (((uintptr_t)d_points | (uintptr_t)d_mp) & 15) return fail(f, ORBX_E_INVALID, who + "d_points and d_mp must be 16-byte aligned");
-  const int chunks = (mcap + kThreads - 1) / kThreads;
-  if ((long long)nitems * chunks > (long long)INT_MAX) return fail(f, ORBX_E_INVALID, who + "too many workgroups");
+  int chunks;
+  if (const char* e = grid_problem((uintptr_t)d_points | (uintptr_t)d_mp, "d_points and d_mp must be 16-byte aligned", nitems, mcap, &chunks))
+    return fail(f, ORBX_E_INVALID, who + e);
   int rc = same_device(f, who.c_str(), {d_points, d_obs, d_items, d_idx, d_nmp, d_mp, d_depth, d_ntomatch}, "the handle");
   if (rc != ORBX_OK) return rc;
   Args g;
@@ -273,7 +172,7 @@ int orbx_frustum_project_device(orbx_frustum* f, const orbx_frustum_point* d_poi
       f->have = true; f->lsf_bits = bits; f->nlevels = nlevels; f->log_kind = log_kind;
     }
   }
-  for (int n = 0; n < kMaxT; n++) g.T[n] = (!g.all_bad && n + 1 < nlevels) ? f->T[n] : INFINITY;
+  fill_levels(g.T, nullptr, g.all_bad ? nullptr : f->T, nullptr, nlevels);
   g.points = (const float4*)d_points; g.obs = d_obs; g.items = d_items; g.idx = d_idx; g.nmp = d_nmp;
   g.mp = (float4*)d_mp; g.depth = d_depth; g.ntomatch = d_ntomatch;
   g.npoints = npoints; g.nitems = nitems; g.mcap = mcap; g.chunks = chunks; g.cos_limit = cos_limit;
@@ -315,7 +214,7 @@ int orbx_frustum_project_reference(const orbx_frustum_point* points, const int32
                                    int sum_order, int log_kind, orbx_localmatch_point* mp, float* depth, int32_t* ntomatch) {
   if (const char* e = call_problem(points, obs, npoints, items, nitems, idx, nmp, mcap, nlevels, cos_limit, sum_order, log_kind, mp, ntomatch))
     return create_fail(ORBX_E_INVALID, "orbx_frustum_project_reference", e);
-  const HostLevel level = {log_scale_factor, nlevels, log_kind};
+  const HostLevel level = {log_scale_factor, nlevels, log_kind, nullptr};
   const HostPoints table = {points};
   const bool all_bad = !usable_lsf(log_scale_factor);
   for (int b = 0; b < nitems; b++) {

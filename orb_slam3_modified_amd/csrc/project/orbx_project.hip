@@ -3,7 +3,9 @@
 // batched matchers read.
 //
 // emit_one<kEmit, kQuat, kTree> is the specification, stated once for the host and the device; what differs is where the level comes from:
-// the host twins call libm's log (HostLevel), the kernel counts the caller's thresholds (DeviceLevel).
+// the host twins call libm's log (HostLevel), the kernel counts the caller's thresholds (DeviceLevel).  Both, sum3, the rigid transform,
+// the table's readers, the check, the lanes' bookkeeping, the level checks, the option dispatch and the twins' loop are the projection-front
+// core's (../side/orbx_front_device.h, orbx_front_host.h), shared with liborbx_frustum.so and liborbx_sim3.so.
 //
 // k_project_check            one workgroup per item: nslots and every index of the row's first nslots against npoints, before any of them
 //                            addresses the table; d_nvalid[b] = -1 (malformed) or 0.
@@ -22,48 +24,19 @@
 #include <string>
 
 #include "../side/orbx_handle.h"
+#include "../side/orbx_front_host.h"
 #include "../../../include/orbx_project.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kMaxLevels = ORBX_FRUSTUM_MAX_LEVELS;
-constexpr int kMaxT = kMaxLevels - 1;
+using namespace orbx::side::front;
 enum { kLast = 0, kReloc = 1, kFuse = 2 };
-static_assert(sizeof(orbx_frustum_point) == 48 && sizeof(orbx_project_item) == 128 && sizeof(orbx_project_slot) == 16, "record sizes");
+static_assert(sizeof(orbx_project_slot) == 16, "record sizes");
 static_assert(sizeof(orbx_lastmatch_point) == 32 && sizeof(orbx_projmatch_point) == 32 && sizeof(orbx_fuse_query) == 32, "row sizes");
-
-struct Row { uint32_t w[8]; };   // a row of any of the three consumers, as its 32-bit words
-__host__ __device__ inline uint32_t fw(float f) { return __builtin_bit_cast(uint32_t, f); }
-__host__ __device__ inline uint32_t iw(int32_t i) { return (uint32_t)i; }
 
 // the skipped row: zero bytes; a fuse query with point = -1
 template <int kEmit>
 __host__ __device__ inline Row skipped_row() { return {{0u, 0u, 0u, 0u, 0u, 0u, kEmit == kFuse ? 0xFFFFFFFFu : 0u, 0u}}; }
-
-template <bool kTree>
-__host__ __device__ inline float sum3(float a, float b, float c) { return kTree ? a + (b + c) : (a + b) + c; }
-
-// Eigen's cross: (a1*b2 - a2*b1, a2*b0 - a0*b2, a0*b1 - a1*b0)
-__host__ __device__ inline void cross3(const float* a, const float* b, float* o) {
-  o[0] = a[1] * b[2] - a[2] * b[1];
-  o[1] = a[2] * b[0] - a[0] * b[2];
-  o[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-// Pc = Tcw * P
-template <bool kQuat, bool kTree>
-__host__ __device__ inline void transform(const orbx_project_item& c, const float* P, float* Pc) {
-  if (kQuat) {
-    float uv[3], x[3];
-    cross3(c.q, P, uv);
-    for (int k = 0; k < 3; k++) uv[k] = uv[k] + uv[k];
-    cross3(c.q, uv, x);
-    for (int k = 0; k < 3; k++) Pc[k] = ((P[k] + c.q[3] * uv[k]) + x[k]) + c.tcw[k];
-  } else {
-    for (int k = 0; k < 3; k++) Pc[k] = sum3<kTree>(c.Rcw[3 * k] * P[0], c.Rcw[3 * k + 1] * P[1], c.Rcw[3 * k + 2] * P[2]) + c.tcw[k];
-  }
-}
 
 // One slot below nslots with point < npoints (the caller's): the emitter's gates and its row.  Returns whether the row is valid.
 template <int kEmit, bool kQuat, bool kTree, class Points, class Level>
@@ -73,7 +46,7 @@ __host__ __device__ inline bool emit_one(const orbx_project_item& c, const Point
   if (point < 0) return false;
   const orbx_frustum_point p = points(point);
   float Pc[3];
-  transform<kQuat, kTree>(c, p.pos, Pc);
+  transform<kQuat, kTree>(c.Rcw, c.tcw, c.q, p.pos, Pc);
   float invz = 0.0f;
   if (kEmit == kLast) {
     invz = 1.0f / Pc[2];
@@ -120,60 +93,10 @@ __host__ __device__ inline bool emit_one(const orbx_project_item& c, const Point
   return true;
 }
 
-// ---------------------------------------------------------------------------------------------------------------- the level on the host
-// int nScale = ceil(log(ratio) / mfLogScaleFactor) under each overload of log, then the clamp; outside the range of int (NaN included)
-// x86's conversion gives INT_MIN, which the clamp raises to 0 (include/orbx_frustum.h, step 9 and Limits)
-struct HostLevel {
-  float lsf; int nlevels, log_kind; const float* sf;
-  void operator()(float ratio, int* lvl, float* scale) const {
-    double q;
-    if (log_kind == ORBX_FRUSTUM_LOG_FLOAT) {
-      const float f = std::log(ratio) / lsf;                    // std::log(float): libm's logf, a float division
-      q = std::ceil((double)f);
-    } else {
-      q = std::ceil(::log((double)ratio) / (double)lsf);        // ::log(double), the float divisor promoted
-    }
-    int n = 0;
-    if (q >= -2147483648.0 && q < 2147483648.0) {
-      n = (int)q;
-      n = n < 0 ? 0 : n >= nlevels ? nlevels - 1 : n;
-    }
-    *lvl = n;
-    *scale = sf ? sf[n] : 0.0f;
-  }
-};
-
-struct HostPoints {
-  const orbx_frustum_point* t;
-  const orbx_frustum_point& operator()(int idx) const { return t[idx]; }
-};
-
-const char* options_problem(int rot_kind, int sum_order) {
-  if (rot_kind != ORBX_PROJECT_ROT_MATRIX && rot_kind != ORBX_PROJECT_ROT_QUAT) return "unknown rot_kind";
-  if (sum_order != ORBX_FRUSTUM_SUM_LTR && sum_order != ORBX_FRUSTUM_SUM_TREE) return "unknown sum_order";
-  return nullptr;
-}
-const char* levels_problem(int nlevels) { return nlevels < 1 || nlevels > kMaxLevels ? "nlevels must be in 1 .. 16" : nullptr; }
-const char* thresholds_problem(const float* T, int nlevels) {
-  if (const char* e = levels_problem(nlevels)) return e;
-  if (!T && nlevels > 1) return "null thresholds";
-  for (int n = 0; n + 1 < nlevels; n++) {
-    if (!std::isfinite(T[n]) || !(T[n] > 0.0f)) return "thresholds must be finite and positive";
-    if (n > 0 && !(T[n] > T[n - 1])) return "thresholds must be strictly increasing";
-  }
-  return nullptr;
-}
-const char* log_problem(float lsf, int nlevels, int log_kind) {
-  if (const char* e = levels_problem(nlevels)) return e;
-  if (log_kind != ORBX_FRUSTUM_LOG_DOUBLE && log_kind != ORBX_FRUSTUM_LOG_FLOAT) return "unknown log_kind";
-  if (!(std::isfinite(lsf) && lsf > 0.0f)) return "log_scale_factor must be finite and positive";
-  return nullptr;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------- the kernels
 struct Args {
   const float4* points; const int32_t* obs; const orbx_project_item* items;
-  const void* slots;     // orbx_project_slot rows, or int32 rows (fuse)
+  const int32_t* slots;  // orbx_project_slot rows, or int32 rows (fuse), as their words
   const int32_t* nslots;
   float4* out; int32_t* nvalid;
   int npoints, nitems, mcap, chunks;
@@ -182,111 +105,49 @@ struct Args {
   float sf[kMaxLevels];  // fuse: the scale factors, the last repeated beyond nlevels - 1
 };
 
-// the number of thresholds below ratio; they ascend strictly, so those are T[0 .. level), and the level's scale factor is picked on the way
-struct DeviceLevel {
-  const float* T; const float* sf;
-  __device__ void operator()(float ratio, int* lvl, float* scale) const {
-    int l = 0;
-    float s = sf[0];
-    if (ratio > 0.0f && ratio != INFINITY) {
-#pragma unroll
-      for (int n = 0; n < kMaxT; n++)
-        if (ratio > T[n]) { l = n + 1; s = sf[n + 1]; }
-    }
-    *lvl = l;
-    *scale = s;
-  }
-};
-struct DevicePoints {
-  const float4* t;
-  __device__ orbx_frustum_point operator()(int idx) const {
-    const float4 a = t[3 * (size_t)idx], b = t[3 * (size_t)idx + 1];
-    const float max_dist = ((const float*)(t + 3 * (size_t)idx + 2))[0];
-    return {{a.x, a.y, a.z}, a.w, {b.x, b.y, b.z}, b.w, max_dist, {0.0f, 0.0f, 0.0f}};
-  }
-};
-
 __global__ __launch_bounds__(kThreads) void k_project_check(Args g) {
   const int b = blockIdx.x;
-  const int n = g.nslots[b];
-  int bad = n < 0 || n > g.mcap;
-  if (!bad) {
-    const int32_t* row = (const int32_t*)g.slots + (size_t)b * g.mcap * g.stride;
-    for (int j = threadIdx.x; j < n; j += kThreads) bad |= row[(size_t)j * g.stride] >= g.npoints;
-  }
-  bad = __syncthreads_or(bad);
-  if (threadIdx.x == 0) g.nvalid[b] = bad ? -1 : 0;
+  check_item(g.slots + (size_t)b * g.mcap * g.stride, g.stride, g.nslots[b], g.mcap, g.npoints, false, g.nvalid + b);
 }
 
 template <int kEmit, bool kQuat, bool kTree>
 __global__ __launch_bounds__(kThreads) void k_project(Args g) {
-  const int b = (int)(blockIdx.x / (unsigned)g.chunks);
-  const int j = (int)(blockIdx.x - (unsigned)b * (unsigned)g.chunks) * kThreads + (int)threadIdx.x;
-  // -1 stays -1: a malformed item adds nothing; a sound one only grows from 0
-  const bool bad = __hip_atomic_load(g.nvalid + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < 0;
-  const int n = bad ? 0 : g.nslots[b];
+  const Lane l = lane_of(g.slots, kEmit == kFuse ? 1 : 4, g.nslots, g.nvalid, g.mcap, g.chunks);
+  Row r = skipped_row<kEmit>();
   bool valid = false;
-  if (j < g.mcap) {
-    const size_t slot = (size_t)b * g.mcap + j;
-    Row r = skipped_row<kEmit>();
-    if (j < n) {
-      int point, octave = 0;
-      float angle = 0.0f;
-      if (kEmit == kFuse) {
-        point = ((const int32_t*)g.slots)[slot];
-      } else {
-        const int4 s = ((const int4*)g.slots)[slot];
-        point = s.x; octave = s.y; angle = __int_as_float(s.z);
-      }
-      valid = emit_one<kEmit, kQuat, kTree>(g.items[b], DevicePoints{g.points}, g.obs, point, octave, angle, DeviceLevel{g.T, g.sf}, &r);
+  if (l.live) {
+    int point = l.point, octave = 0;
+    float angle = 0.0f;
+    if (kEmit != kFuse) {
+      const int4 s = *(const int4*)l.s;
+      point = s.x; octave = s.y; angle = __int_as_float(s.z);
     }
-    g.out[2 * slot] = make_float4(__uint_as_float(r.w[0]), __uint_as_float(r.w[1]), __uint_as_float(r.w[2]), __uint_as_float(r.w[3]));
-    g.out[2 * slot + 1] = make_float4(__uint_as_float(r.w[4]), __uint_as_float(r.w[5]), __uint_as_float(r.w[6]), __uint_as_float(r.w[7]));
+    valid = emit_one<kEmit, kQuat, kTree>(g.items[l.b], DevicePoints{g.points}, g.obs, point, octave, angle, DeviceLevel{g.T, g.sf}, &r);
   }
-  const int count = __popcll(__ballot(valid));
-  if (count > 0 && (threadIdx.x & 63) == 0) atomicAdd(g.nvalid + b, count);
+  finish(l, g.out, g.nvalid, r, valid);
 }
 
 template <int kEmit>
 void launch(const Args& g, int rot_kind, int sum_order, hipStream_t st) {
-  const dim3 grid((unsigned)(g.nitems * g.chunks)), block(kThreads);
-  const bool quat = rot_kind == ORBX_PROJECT_ROT_QUAT, tree = sum_order == ORBX_FRUSTUM_SUM_TREE;
-  if (quat && tree) hipLaunchKernelGGL((k_project<kEmit, true, true>), grid, block, 0, st, g);
-  else if (quat) hipLaunchKernelGGL((k_project<kEmit, true, false>), grid, block, 0, st, g);
-  else if (tree) hipLaunchKernelGGL((k_project<kEmit, false, true>), grid, block, 0, st, g);
-  else hipLaunchKernelGGL((k_project<kEmit, false, false>), grid, block, 0, st, g);
+  dispatch(rot_kind, sum_order, [&](auto q, auto t) {
+    hipLaunchKernelGGL((k_project<kEmit, q(), t()>), dim3((unsigned)(g.nitems * g.chunks)), dim3(kThreads), 0, st, g);
+  });
 }
 
-// the host twin of one emitter: the check and the per-slot loop
+// the host twin of one emitter
 template <int kEmit>
-void reference(const orbx_frustum_point* points, const int32_t* obs, int npoints, const orbx_project_item* items, int nitems, const void* slots,
-               const int32_t* nslots, int mcap, const HostLevel& level, int rot_kind, int sum_order, void* out, int32_t* nvalid) {
-  const int stride = kEmit == kFuse ? 1 : 4;
-  const HostPoints table = {points};
-  const bool quat = rot_kind == ORBX_PROJECT_ROT_QUAT, tree = sum_order == ORBX_FRUSTUM_SUM_TREE;
-  for (int b = 0; b < nitems; b++) {
-    const int32_t* row = (const int32_t*)slots + (size_t)b * mcap * stride;
-    bool bad = nslots[b] < 0 || nslots[b] > mcap;
-    for (int j = 0; !bad && j < nslots[b]; j++) bad = row[(size_t)j * stride] >= npoints;
-    const int n = bad ? 0 : nslots[b];
-    int count = 0;
-    for (int j = 0; j < mcap; j++) {
-      Row r = skipped_row<kEmit>();
-      if (j < n) {
-        const int32_t* s = row + (size_t)j * stride;
-        const int point = s[0], octave = kEmit == kFuse ? 0 : s[1];
-        float angle = 0.0f;
-        if (kEmit != kFuse) memcpy(&angle, s + 2, 4);
-        const orbx_project_item& c = items[b];
-        count += quat ? (tree ? emit_one<kEmit, true, true>(c, table, obs, point, octave, angle, level, &r)
-                              : emit_one<kEmit, true, false>(c, table, obs, point, octave, angle, level, &r))
-                      : (tree ? emit_one<kEmit, false, true>(c, table, obs, point, octave, angle, level, &r)
-                              : emit_one<kEmit, false, false>(c, table, obs, point, octave, angle, level, &r));
-      }
-      memcpy((uint8_t*)out + ((size_t)b * mcap + j) * sizeof(Row), &r, sizeof(Row));
-    }
-    nvalid[b] = bad ? -1 : count;
-  }
+void twin(const orbx_frustum_point* points, const int32_t* obs, int npoints, const orbx_project_item* items, int nitems, const void* slots,
+          const int32_t* nslots, int mcap, const HostLevel& level, int rot_kind, int sum_order, void* out, int32_t* nvalid) {
+  dispatch(rot_kind, sum_order, [&](auto q, auto t) {
+    constexpr bool kQuat = q(), kTree = t();
+    reference((const int32_t*)slots, kEmit == kFuse ? 1 : 4, nslots, nitems, mcap, npoints, skipped_row<kEmit>(), out, nvalid,
+              [&](int b, const int32_t* s, Row* r) {
+                const int octave = kEmit == kFuse ? 0 : s[1];
+                float angle = 0.0f;
+                if (kEmit != kFuse) memcpy(&angle, s + 2, 4);
+                return emit_one<kEmit, kQuat, kTree>(items[b], HostPoints{points}, obs, s[0], octave, angle, level, r);
+              });
+  });
 }
 
 }  // namespace
@@ -300,12 +161,10 @@ using namespace orbx::side;
 // what every form checks before anything is computed, copied or launched; the reason, or nullptr.  `obs` is an argument of last alone
 const char* call_problem(const void* points, const void* obs, bool wants_obs, int npoints, const void* items, int nitems, const void* slots,
                          const void* nslots, int mcap, int rot_kind, int sum_order, const void* out, const void* nvalid) {
-  if (!points || (wants_obs && !obs) || !items || !slots || !nslots) return "null points, obs, items, slots or nslots";
-  if (!out || !nvalid) return "null out or nvalid";
-  if (npoints < 1 || nitems < 1 || mcap < 1) return "npoints, nitems and mcap must be at least 1";
-  if (const char* e = options_problem(rot_kind, sum_order)) return e;
-  if ((long long)nitems * mcap > (long long)INT_MAX) return "nitems * mcap exceeds INT_MAX";
-  return nullptr;
+  const char* missing = !points || (wants_obs && !obs) || !items || !slots || !nslots ? "null points, obs, items, slots or nslots"
+                        : !out || !nvalid                                               ? "null out or nvalid" : nullptr;
+  const char* own = rot_problem(rot_kind);
+  return common_problem(missing, npoints, nitems, mcap, own ? own : sum_problem(sum_order));
 }
 
 // the device form of every emitter, after call_problem and the emitter's own checks
@@ -313,16 +172,15 @@ template <int kEmit>
 int project_device(orbx_project* p, const std::string& who, const void* d_points, const int32_t* d_obs, int npoints, const orbx_project_item* d_items,
                    int nitems, const void* d_slots, const int32_t* d_nslots, int mcap, const float* thresholds, const float* scale_factors,
                    int nlevels, int rot_kind, int sum_order, void* d_out, int32_t* d_nvalid, void* stream) {
-  if (((uintptr_t)d_points | (uintptr_t)d_out | (kEmit == kFuse ? 0 : (uintptr_t)d_slots)) & 15)
-    return fail(p, ORBX_E_INVALID, who + "d_points, d_slots and d_out must be 16-byte aligned");
-  const int chunks = (mcap + kThreads - 1) / kThreads;
-  if ((long long)nitems * chunks > (long long)INT_MAX) return fail(p, ORBX_E_INVALID, who + "too many workgroups");
+  int chunks;
+  if (const char* e = grid_problem((uintptr_t)d_points | (uintptr_t)d_out | (kEmit == kFuse ? 0 : (uintptr_t)d_slots),
+                                   "d_points, d_slots and d_out must be 16-byte aligned", nitems, mcap, &chunks))
+    return fail(p, ORBX_E_INVALID, who + e);
   int rc = same_device(p, who.c_str(), {d_points, d_obs, d_items, d_slots, d_nslots, d_out, d_nvalid}, "the handle");
   if (rc != ORBX_OK) return rc;
   Args g;
-  for (int n = 0; n < kMaxT; n++) g.T[n] = (thresholds && n + 1 < nlevels) ? thresholds[n] : INFINITY;
-  for (int n = 0; n < kMaxLevels; n++) g.sf[n] = scale_factors ? scale_factors[n < nlevels ? n : nlevels - 1] : 0.0f;
-  g.points = (const float4*)d_points; g.obs = d_obs; g.items = d_items; g.slots = d_slots; g.nslots = d_nslots;
+  fill_levels(g.T, g.sf, thresholds, scale_factors, nlevels);
+  g.points = (const float4*)d_points; g.obs = d_obs; g.items = d_items; g.slots = (const int32_t*)d_slots; g.nslots = d_nslots;
   g.out = (float4*)d_out; g.nvalid = d_nvalid;
   g.npoints = npoints; g.nitems = nitems; g.mcap = mcap; g.chunks = chunks; g.stride = kEmit == kFuse ? 1 : 4;
   ORBX_SIDE_HIP(p, hipSetDevice(p->device));
@@ -394,7 +252,7 @@ int orbx_project_last_reference(const orbx_frustum_point* points, const int32_t*
                                 orbx_lastmatch_point* out, int32_t* nvalid) {
   if (const char* e = call_problem(points, obs, true, npoints, items, nitems, slots, nslots, mcap, rot_kind, sum_order, out, nvalid))
     return create_fail(ORBX_E_INVALID, "orbx_project_last_reference", e);
-  reference<kLast>(points, obs, npoints, items, nitems, slots, nslots, mcap, HostLevel{1.0f, 1, 0, nullptr}, rot_kind, sum_order, out, nvalid);
+  twin<kLast>(points, obs, npoints, items, nitems, slots, nslots, mcap, HostLevel{1.0f, 1, 0, nullptr}, rot_kind, sum_order, out, nvalid);
   return ORBX_OK;
 }
 
@@ -429,7 +287,7 @@ int orbx_project_reloc_reference(const orbx_frustum_point* points, int npoints, 
   const char* e = call_problem(points, nullptr, false, npoints, items, nitems, slots, nslots, mcap, rot_kind, sum_order, out, nvalid);
   if (!e) e = log_problem(log_scale_factor, nlevels, log_kind);
   if (e) return create_fail(ORBX_E_INVALID, "orbx_project_reloc_reference", e);
-  reference<kReloc>(points, nullptr, npoints, items, nitems, slots, nslots, mcap, HostLevel{log_scale_factor, nlevels, log_kind, nullptr}, rot_kind,
+  twin<kReloc>(points, nullptr, npoints, items, nitems, slots, nslots, mcap, HostLevel{log_scale_factor, nlevels, log_kind, nullptr}, rot_kind,
                     sum_order, out, nvalid);
   return ORBX_OK;
 }
@@ -468,7 +326,7 @@ int orbx_project_fuse_reference(const orbx_frustum_point* points, int npoints, c
   if (!e) e = log_problem(log_scale_factor, nlevels, log_kind);
   if (!e && !scale_factors) e = "null scale_factors";
   if (e) return create_fail(ORBX_E_INVALID, "orbx_project_fuse_reference", e);
-  reference<kFuse>(points, nullptr, npoints, items, nitems, idx, nslots, mcap, HostLevel{log_scale_factor, nlevels, log_kind, scale_factors}, rot_kind,
+  twin<kFuse>(points, nullptr, npoints, items, nitems, idx, nslots, mcap, HostLevel{log_scale_factor, nlevels, log_kind, scale_factors}, rot_kind,
                    sum_order, out, nvalid);
   return ORBX_OK;
 }

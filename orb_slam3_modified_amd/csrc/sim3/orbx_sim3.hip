@@ -4,8 +4,9 @@
 //
 // emit_pose<kEmit, kQuat, kTree> (proj in its two forms, fuse) and emit_search<kQuat, kTree, kSimQuat> are the specification, each stated
 // once for the host and the device; what differs is where the level comes from: the host twins call libm's log (HostLevel), the kernels
-// count the caller's thresholds (DeviceLevel).  sum3, the two rotation forms, the counting level and the slot check are this file's own statement of what
-// csrc/project/orbx_project.hip states for the SE3 callers: that file is pinned as it stands, so nothing was moved out of it.
+// count the caller's thresholds (DeviceLevel).  Both, sum3, the rigid transform, the table's readers, the check, the lanes' bookkeeping, the
+// level checks, the option dispatch and the twins' loop are the projection-front core's (../side/orbx_front_device.h, orbx_front_host.h),
+// shared with liborbx_frustum.so and liborbx_project.so.
 //
 // k_sim3_check               one workgroup per item: nslots and every index of the row's first nslots against npoints, before any of them
 //                            addresses the table; d_nvalid[b] = -1 (malformed) or 0.
@@ -26,49 +27,19 @@
 #include <string>
 
 #include "../side/orbx_handle.h"
+#include "../side/orbx_front_host.h"
 #include "../../../include/orbx_sim3.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kMaxLevels = ORBX_FRUSTUM_MAX_LEVELS;
-constexpr int kMaxT = kMaxLevels - 1;
+using namespace orbx::side::front;
 enum { kProj = 0, kFuse = 1, kSearch = 2, kProjKfs = 3 };   // kProjKfs: the vpPointsKFs overload, which projects as SearchBySim3 does
-static_assert(sizeof(orbx_frustum_point) == 48 && sizeof(orbx_project_item) == 128 && sizeof(orbx_sim3_item) == 176, "record sizes");
+static_assert(sizeof(orbx_sim3_item) == 176, "record sizes");
 static_assert(sizeof(orbx_projmatch_point) == 32 && sizeof(orbx_fuse_query) == 32, "row sizes");
-
-struct Row { uint32_t w[8]; };   // a row of either consumer, as its 32-bit words
-typedef uint32_t Words4 __attribute__((ext_vector_type(4)));
-__host__ __device__ inline uint32_t fw(float f) { return __builtin_bit_cast(uint32_t, f); }
-__host__ __device__ inline uint32_t iw(int32_t i) { return (uint32_t)i; }
 
 // the skipped row: zero bytes; a query with point = -1
 template <int kEmit>
 __host__ __device__ inline Row skipped_row() { return {{0u, 0u, 0u, 0u, 0u, 0u, kEmit == kProj || kEmit == kProjKfs ? 0u : 0xFFFFFFFFu, 0u}}; }
-
-template <bool kTree>
-__host__ __device__ inline float sum3(float a, float b, float c) { return kTree ? a + (b + c) : (a + b) + c; }
-
-// Eigen's cross: (a1*b2 - a2*b1, a2*b0 - a0*b2, a0*b1 - a1*b0)
-__host__ __device__ inline void cross3(const float* a, const float* b, float* o) {
-  o[0] = a[1] * b[2] - a[2] * b[1];
-  o[1] = a[2] * b[0] - a[0] * b[2];
-  o[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-// Pc = T * P for a rigid pose (R, t, unit q)
-template <bool kQuat, bool kTree>
-__host__ __device__ inline void transform(const float* R, const float* t, const float* q, const float* P, float* Pc) {
-  if (kQuat) {
-    float uv[3], x[3];
-    cross3(q, P, uv);
-    for (int k = 0; k < 3; k++) uv[k] = uv[k] + uv[k];
-    cross3(q, uv, x);
-    for (int k = 0; k < 3; k++) Pc[k] = ((P[k] + q[3] * uv[k]) + x[k]) + t[k];
-  } else {
-    for (int k = 0; k < 3; k++) Pc[k] = sum3<kTree>(R[3 * k] * P[0], R[3 * k + 1] * P[1], R[3 * k + 2] * P[2]) + t[k];
-  }
-}
 
 // Pb = S * Pa for a similarity (s, R, t, the RxSO3's quaternion q)
 template <bool kSimQuat, bool kTree>
@@ -168,57 +139,13 @@ struct Match2 {   // vnMatch2 of one pair
   __host__ __device__ int operator()(int i2) const { return dist[i2] <= th_high ? idx[i2] : -1; }
 };
 
-// ---------------------------------------------------------------------------------------------------------------- the level on the host
-// int nScale = ceil(log(ratio) / mfLogScaleFactor) under each overload of log, then the clamp; outside the range of int (NaN included)
-// x86's conversion gives INT_MIN, which the clamp raises to 0 (include/orbx_frustum.h, step 9 and Limits)
-struct HostLevel {
-  float lsf; int nlevels, log_kind; const float* sf;
-  void operator()(float ratio, int* lvl, float* scale) const {
-    double q;
-    if (log_kind == ORBX_FRUSTUM_LOG_FLOAT) {
-      const float f = std::log(ratio) / lsf;                    // std::log(float): libm's logf, a float division
-      q = std::ceil((double)f);
-    } else {
-      q = std::ceil(::log((double)ratio) / (double)lsf);        // ::log(double), the float divisor promoted
-    }
-    int n = 0;
-    if (q >= -2147483648.0 && q < 2147483648.0) {
-      n = (int)q;
-      n = n < 0 ? 0 : n >= nlevels ? nlevels - 1 : n;
-    }
-    *lvl = n;
-    *scale = sf ? sf[n] : 0.0f;
-  }
-};
-
-struct HostPoints {
-  const orbx_frustum_point* t;
-  const orbx_frustum_point& operator()(int idx) const { return t[idx]; }
-};
-
 const char* proj_problem(int proj_kind) {
   return proj_kind != ORBX_SIM3_PROJ_DIVIDE && proj_kind != ORBX_SIM3_PROJ_INVZ ? "unknown proj_kind" : nullptr;
 }
 const char* options_problem(int rot_kind, int sum_order, int sim_kind) {
-  if (rot_kind != ORBX_PROJECT_ROT_MATRIX && rot_kind != ORBX_PROJECT_ROT_QUAT) return "unknown rot_kind";
-  if (sum_order != ORBX_FRUSTUM_SUM_LTR && sum_order != ORBX_FRUSTUM_SUM_TREE) return "unknown sum_order";
+  if (const char* e = rot_problem(rot_kind)) return e;
+  if (const char* e = sum_problem(sum_order)) return e;
   if (sim_kind != ORBX_SIM3_MATRIX && sim_kind != ORBX_SIM3_QUAT) return "unknown sim_kind";
-  return nullptr;
-}
-const char* levels_problem(int nlevels) { return nlevels < 1 || nlevels > kMaxLevels ? "nlevels must be in 1 .. 16" : nullptr; }
-const char* thresholds_problem(const float* T, int nlevels) {
-  if (const char* e = levels_problem(nlevels)) return e;
-  if (!T && nlevels > 1) return "null thresholds";
-  for (int n = 0; n + 1 < nlevels; n++) {
-    if (!std::isfinite(T[n]) || !(T[n] > 0.0f)) return "thresholds must be finite and positive";
-    if (n > 0 && !(T[n] > T[n - 1])) return "thresholds must be strictly increasing";
-  }
-  return nullptr;
-}
-const char* log_problem(float lsf, int nlevels, int log_kind) {
-  if (const char* e = levels_problem(nlevels)) return e;
-  if (log_kind != ORBX_FRUSTUM_LOG_DOUBLE && log_kind != ORBX_FRUSTUM_LOG_FLOAT) return "unknown log_kind";
-  if (!(std::isfinite(lsf) && lsf > 0.0f)) return "log_scale_factor must be finite and positive";
   return nullptr;
 }
 
@@ -233,107 +160,37 @@ struct Args {
   float sf[kMaxLevels];  // the scale factors, the last repeated beyond nlevels - 1 (proj: zeros, not read)
 };
 
-// the number of thresholds below ratio; they ascend strictly, so those are T[0 .. level), and the level's scale factor is picked on the way
-struct DeviceLevel {
-  const float* T; const float* sf;
-  __device__ void operator()(float ratio, int* lvl, float* scale) const {
-    int l = 0;
-    float s = sf[0];
-    if (ratio > 0.0f && ratio != INFINITY) {
-#pragma unroll
-      for (int n = 0; n < kMaxT; n++)
-        if (ratio > T[n]) { l = n + 1; s = sf[n + 1]; }
-    }
-    *lvl = l;
-    *scale = s;
-  }
-};
-struct DevicePoints {
-  const float4* t;
-  __device__ orbx_frustum_point operator()(int idx) const {
-    const float4 a = t[3 * (size_t)idx], b = t[3 * (size_t)idx + 1];
-    const float max_dist = ((const float*)(t + 3 * (size_t)idx + 2))[0];
-    return {{a.x, a.y, a.z}, a.w, {b.x, b.y, b.z}, b.w, max_dist, {0.0f, 0.0f, 0.0f}};
-  }
-};
-
 __global__ __launch_bounds__(kThreads) void k_sim3_check(Args g) {
   const int b = blockIdx.x;
-  const int n = g.nslots[b];
-  int bad = n < 0 || n > g.mcap;
-  if (!bad) {
-    const int32_t* row = g.idx + (size_t)b * g.mcap;
-    for (int j = threadIdx.x; j < n; j += kThreads) bad |= row[j] >= g.npoints;
-  }
-  bad = __syncthreads_or(bad);
-  if (threadIdx.x == 0) g.nvalid[b] = bad ? -1 : 0;
-}
-
-// what the two emitter kernels share: the lane's slot, its index (or "none"), the row's stores and the count
-struct Lane { int b, j, point; bool live; size_t slot; };
-__device__ inline Lane lane_of(const Args& g) {
-  Lane l;
-  l.b = (int)(blockIdx.x / (unsigned)g.chunks);
-  l.j = (int)(blockIdx.x - (unsigned)l.b * (unsigned)g.chunks) * kThreads + (int)threadIdx.x;
-  // -1 stays -1: a malformed item adds nothing; a sound one only grows from 0
-  const bool bad = __hip_atomic_load(g.nvalid + l.b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < 0;
-  const int n = bad ? 0 : g.nslots[l.b];
-  l.slot = (size_t)l.b * g.mcap + (l.j < g.mcap ? l.j : 0);
-  l.live = l.j < n;                       // n <= mcap
-  l.point = l.live ? g.idx[l.slot] : -1;
-  return l;
-}
-__device__ inline void finish(const Args& g, const Lane& l, const Row& r, bool valid) {
-  if (l.j < g.mcap) {
-    Words4* const o = (Words4*)g.out + 2 * l.slot;   // native vectors: each half of the row stays one 16-byte store, whatever fields are constant
-    o[0] = Words4{r.w[0], r.w[1], r.w[2], r.w[3]};
-    o[1] = Words4{r.w[4], r.w[5], r.w[6], r.w[7]};
-  }
-  const int count = __popcll(__ballot(valid));
-  if (count > 0 && (threadIdx.x & 63) == 0) atomicAdd(g.nvalid + l.b, count);
+  check_item(g.idx + (size_t)b * g.mcap, 1, g.nslots[b], g.mcap, g.npoints, false, g.nvalid + b);
 }
 
 template <int kEmit, bool kQuat, bool kTree>
 __global__ __launch_bounds__(kThreads) void k_sim3_pose(Args g) {
-  const Lane l = lane_of(g);
+  const Lane l = lane_of(g.idx, 1, g.nslots, g.nvalid, g.mcap, g.chunks);
   Row r = skipped_row<kEmit>();
   bool valid = false;
   if (l.live) valid = emit_pose<kEmit, kQuat, kTree>(((const orbx_project_item*)g.items)[l.b], DevicePoints{g.points}, l.point, DeviceLevel{g.T, g.sf}, &r);
-  finish(g, l, r, valid);
+  finish(l, g.out, g.nvalid, r, valid);
 }
 
 template <bool kQuat, bool kTree, bool kSimQuat>
 __global__ __launch_bounds__(kThreads) void k_sim3_search(Args g) {
-  const Lane l = lane_of(g);
+  const Lane l = lane_of(g.idx, 1, g.nslots, g.nvalid, g.mcap, g.chunks);
   Row r = skipped_row<kSearch>();
   bool valid = false;
   if (l.live) valid = emit_search<kQuat, kTree, kSimQuat>(((const orbx_sim3_item*)g.items)[l.b], DevicePoints{g.points}, l.point, DeviceLevel{g.T, g.sf}, &r);
-  finish(g, l, r, valid);
+  finish(l, g.out, g.nvalid, r, valid);
 }
 
 template <int kEmit>
-void launch_pose(const Args& g, int rot_kind, int sum_order, hipStream_t st) {
-  const dim3 grid((unsigned)(g.nitems * g.chunks)), block(kThreads);
-  const bool quat = rot_kind == ORBX_PROJECT_ROT_QUAT, tree = sum_order == ORBX_FRUSTUM_SUM_TREE;
-  if (quat && tree) hipLaunchKernelGGL((k_sim3_pose<kEmit, true, true>), grid, block, 0, st, g);
-  else if (quat) hipLaunchKernelGGL((k_sim3_pose<kEmit, true, false>), grid, block, 0, st, g);
-  else if (tree) hipLaunchKernelGGL((k_sim3_pose<kEmit, false, true>), grid, block, 0, st, g);
-  else hipLaunchKernelGGL((k_sim3_pose<kEmit, false, false>), grid, block, 0, st, g);
-}
-template <bool kSimQuat>
-void launch_search(const Args& g, int rot_kind, int sum_order, hipStream_t st) {
-  const dim3 grid((unsigned)(g.nitems * g.chunks)), block(kThreads);
-  const bool quat = rot_kind == ORBX_PROJECT_ROT_QUAT, tree = sum_order == ORBX_FRUSTUM_SUM_TREE;
-  if (quat && tree) hipLaunchKernelGGL((k_sim3_search<true, true, kSimQuat>), grid, block, 0, st, g);
-  else if (quat) hipLaunchKernelGGL((k_sim3_search<true, false, kSimQuat>), grid, block, 0, st, g);
-  else if (tree) hipLaunchKernelGGL((k_sim3_search<false, true, kSimQuat>), grid, block, 0, st, g);
-  else hipLaunchKernelGGL((k_sim3_search<false, false, kSimQuat>), grid, block, 0, st, g);
-}
-template <int kEmit>
 void launch(const Args& g, int rot_kind, int sum_order, int sim_kind, hipStream_t st) {
-  if constexpr (kEmit != kSearch) launch_pose<kEmit>(g, rot_kind, sum_order, st);
-  else if (sim_kind == ORBX_SIM3_QUAT) launch_search<true>(g, rot_kind, sum_order, st);
-  else launch_search<false>(g, rot_kind, sum_order, st);
+  const dim3 grid((unsigned)(g.nitems * g.chunks)), block(kThreads);
+  dispatch(rot_kind, sum_order, [&](auto q, auto t) {
+    constexpr bool kQuat = q(), kTree = t();
+    if constexpr (kEmit != kSearch) hipLaunchKernelGGL((k_sim3_pose<kEmit, kQuat, kTree>), grid, block, 0, st, g);
+    else pick(sim_kind == ORBX_SIM3_QUAT, [&](auto s) { hipLaunchKernelGGL((k_sim3_search<kQuat, kTree, s()>), grid, block, 0, st, g); });
+  });
 }
 
 struct AgreeArgs {
@@ -362,45 +219,22 @@ __global__ __launch_bounds__(kThreads) void k_sim3_agree(AgreeArgs g) {
   if (count > 0 && (threadIdx.x & 63) == 0) atomicAdd(g.nfound + p, count);
 }
 
-// the host twin of one emitter: the check and the per-slot loop
+// the host twin of one emitter
 template <int kEmit>
-void reference(const orbx_frustum_point* points, int npoints, const void* items, int nitems, const int32_t* idx, const int32_t* nslots, int mcap,
-               const HostLevel& level, int rot_kind, int sum_order, int sim_kind, void* out, int32_t* nvalid) {
+void twin(const orbx_frustum_point* points, int npoints, const void* items, int nitems, const int32_t* idx, const int32_t* nslots, int mcap,
+          const HostLevel& level, int rot_kind, int sum_order, int sim_kind, void* out, int32_t* nvalid) {
   const HostPoints table = {points};
-  const bool quat = rot_kind == ORBX_PROJECT_ROT_QUAT, tree = sum_order == ORBX_FRUSTUM_SUM_TREE, simq = sim_kind == ORBX_SIM3_QUAT;
-  for (int b = 0; b < nitems; b++) {
-    const int32_t* row = idx + (size_t)b * mcap;
-    bool bad = nslots[b] < 0 || nslots[b] > mcap;
-    for (int j = 0; !bad && j < nslots[b]; j++) bad = row[j] >= npoints;
-    const int n = bad ? 0 : nslots[b];
-    int count = 0;
-    for (int j = 0; j < mcap; j++) {
-      Row r = skipped_row<kEmit>();
-      if (j < n) {
-        const int point = row[j];
-        if constexpr (kEmit == kSearch) {
-          const orbx_sim3_item& c = ((const orbx_sim3_item*)items)[b];
-          const int o = (quat ? 4 : 0) | (tree ? 2 : 0) | (simq ? 1 : 0);
-          switch (o) {
-            case 0: count += emit_search<false, false, false>(c, table, point, level, &r); break;
-            case 1: count += emit_search<false, false, true>(c, table, point, level, &r); break;
-            case 2: count += emit_search<false, true, false>(c, table, point, level, &r); break;
-            case 3: count += emit_search<false, true, true>(c, table, point, level, &r); break;
-            case 4: count += emit_search<true, false, false>(c, table, point, level, &r); break;
-            case 5: count += emit_search<true, false, true>(c, table, point, level, &r); break;
-            case 6: count += emit_search<true, true, false>(c, table, point, level, &r); break;
-            default: count += emit_search<true, true, true>(c, table, point, level, &r); break;
-          }
-        } else {
-          const orbx_project_item& c = ((const orbx_project_item*)items)[b];
-          count += quat ? (tree ? emit_pose<kEmit, true, true>(c, table, point, level, &r) : emit_pose<kEmit, true, false>(c, table, point, level, &r))
-                        : (tree ? emit_pose<kEmit, false, true>(c, table, point, level, &r) : emit_pose<kEmit, false, false>(c, table, point, level, &r));
-        }
-      }
-      memcpy((uint8_t*)out + ((size_t)b * mcap + j) * sizeof(Row), &r, sizeof(Row));
-    }
-    nvalid[b] = bad ? -1 : count;
-  }
+  dispatch(rot_kind, sum_order, [&](auto q, auto t) {
+    constexpr bool kQuat = q(), kTree = t();
+    auto loop = [&](auto emit) { reference(idx, 1, nslots, nitems, mcap, npoints, skipped_row<kEmit>(), out, nvalid, emit); };
+    if constexpr (kEmit != kSearch)
+      loop([&](int b, const int32_t* s, Row* r) { return emit_pose<kEmit, kQuat, kTree>(((const orbx_project_item*)items)[b], table, s[0], level, r); });
+    else
+      pick(sim_kind == ORBX_SIM3_QUAT, [&](auto sq) {
+        constexpr bool kSimQuat = sq();
+        loop([&](int b, const int32_t* s, Row* r) { return emit_search<kQuat, kTree, kSimQuat>(((const orbx_sim3_item*)items)[b], table, s[0], level, r); });
+      });
+  });
 }
 
 }  // namespace
@@ -414,12 +248,8 @@ using namespace orbx::side;
 // what every emitter form checks before anything is computed, copied or launched; the reason, or nullptr
 const char* call_problem(const void* points, int npoints, const void* items, int nitems, const void* idx, const void* nslots, int mcap, int rot_kind,
                          int sum_order, int sim_kind, const void* out, const void* nvalid) {
-  if (!points || !items || !idx || !nslots) return "null points, items, idx or nslots";
-  if (!out || !nvalid) return "null out or nvalid";
-  if (npoints < 1 || nitems < 1 || mcap < 1) return "npoints, nitems and mcap must be at least 1";
-  if (const char* e = options_problem(rot_kind, sum_order, sim_kind)) return e;
-  if ((long long)nitems * mcap > (long long)INT_MAX) return "nitems * mcap exceeds INT_MAX";
-  return nullptr;
+  const char* missing = !points || !items || !idx || !nslots ? "null points, items, idx or nslots" : !out || !nvalid ? "null out or nvalid" : nullptr;
+  return common_problem(missing, npoints, nitems, mcap, options_problem(rot_kind, sum_order, sim_kind));
 }
 // ... and what the three forms of agree check
 const char* agree_problem(const void* i12, const void* d12, const void* f12, const void* i21, const void* d21, const void* f21, const void* n1,
@@ -436,15 +266,14 @@ template <int kEmit>
 int emit_device(orbx_sim3* p, const std::string& who, const void* d_points, int npoints, const void* d_items, int nitems, const int32_t* d_idx,
                 const int32_t* d_nslots, int mcap, const float* thresholds, const float* scale_factors, int nlevels, int rot_kind, int sum_order,
                 int sim_kind, void* d_out, int32_t* d_nvalid, void* stream) {
-  if (((uintptr_t)d_points | (uintptr_t)d_out | (uintptr_t)d_items) & 15)
-    return fail(p, ORBX_E_INVALID, who + "d_points, d_items and d_out must be 16-byte aligned");
-  const int chunks = (mcap + kThreads - 1) / kThreads;
-  if ((long long)nitems * chunks > (long long)INT_MAX) return fail(p, ORBX_E_INVALID, who + "too many workgroups");
+  int chunks;
+  if (const char* e = grid_problem((uintptr_t)d_points | (uintptr_t)d_out | (uintptr_t)d_items, "d_points, d_items and d_out must be 16-byte aligned",
+                                   nitems, mcap, &chunks))
+    return fail(p, ORBX_E_INVALID, who + e);
   int rc = same_device(p, who.c_str(), {d_points, d_items, d_idx, d_nslots, d_out, d_nvalid}, "the handle");
   if (rc != ORBX_OK) return rc;
   Args g;
-  for (int n = 0; n < kMaxT; n++) g.T[n] = (thresholds && n + 1 < nlevels) ? thresholds[n] : INFINITY;
-  for (int n = 0; n < kMaxLevels; n++) g.sf[n] = scale_factors ? scale_factors[n < nlevels ? n : nlevels - 1] : 0.0f;
+  fill_levels(g.T, g.sf, thresholds, scale_factors, nlevels);
   g.points = (const float4*)d_points; g.items = d_items; g.idx = d_idx; g.nslots = d_nslots;
   g.out = (float4*)d_out; g.nvalid = d_nvalid;
   g.npoints = npoints; g.nitems = nitems; g.mcap = mcap; g.chunks = chunks;
@@ -528,8 +357,8 @@ int orbx_sim3_proj_reference(const orbx_frustum_point* points, int npoints, cons
   if (!e) e = log_problem(log_scale_factor, nlevels, log_kind);
   if (e) return create_fail(ORBX_E_INVALID, "orbx_sim3_proj_reference", e);
   const HostLevel level = {log_scale_factor, nlevels, log_kind, nullptr};
-  if (proj_kind == ORBX_SIM3_PROJ_INVZ) reference<kProjKfs>(points, npoints, items, nitems, idx, nslots, mcap, level, rot_kind, sum_order, 0, out, nvalid);
-  else reference<kProj>(points, npoints, items, nitems, idx, nslots, mcap, level, rot_kind, sum_order, 0, out, nvalid);
+  if (proj_kind == ORBX_SIM3_PROJ_INVZ) twin<kProjKfs>(points, npoints, items, nitems, idx, nslots, mcap, level, rot_kind, sum_order, 0, out, nvalid);
+  else twin<kProj>(points, npoints, items, nitems, idx, nslots, mcap, level, rot_kind, sum_order, 0, out, nvalid);
   return ORBX_OK;
 }
 
@@ -567,7 +396,7 @@ int orbx_sim3_fuse_reference(const orbx_frustum_point* points, int npoints, cons
   if (!e) e = log_problem(log_scale_factor, nlevels, log_kind);
   if (!e && !scale_factors) e = "null scale_factors";
   if (e) return create_fail(ORBX_E_INVALID, "orbx_sim3_fuse_reference", e);
-  reference<kFuse>(points, npoints, items, nitems, idx, nslots, mcap, HostLevel{log_scale_factor, nlevels, log_kind, scale_factors}, rot_kind,
+  twin<kFuse>(points, npoints, items, nitems, idx, nslots, mcap, HostLevel{log_scale_factor, nlevels, log_kind, scale_factors}, rot_kind,
                    sum_order, 0, out, nvalid);
   return ORBX_OK;
 }
@@ -606,7 +435,7 @@ int orbx_sim3_search_reference(const orbx_frustum_point* points, int npoints, co
   if (!e) e = log_problem(log_scale_factor, nlevels, log_kind);
   if (!e && !scale_factors) e = "null scale_factors";
   if (e) return create_fail(ORBX_E_INVALID, "orbx_sim3_search_reference", e);
-  reference<kSearch>(points, npoints, items, nitems, idx, nslots, mcap, HostLevel{log_scale_factor, nlevels, log_kind, scale_factors}, rot_kind,
+  twin<kSearch>(points, npoints, items, nitems, idx, nslots, mcap, HostLevel{log_scale_factor, nlevels, log_kind, scale_factors}, rot_kind,
                      sum_order, sim_kind, out, nvalid);
   return ORBX_OK;
 }
@@ -620,8 +449,8 @@ int orbx_sim3_agree_device(orbx_sim3* p, const int32_t* d_best_idx12, const int3
   if (const char* e = agree_problem(d_best_idx12, d_best_dist12, d_nfound12, d_best_idx21, d_best_dist21, d_nfound21, d_n1, d_n2, npairs, qcap,
                                     d_match12, d_nfound))
     return fail(p, ORBX_E_INVALID, who + e);
-  const int chunks = (qcap + kThreads - 1) / kThreads;
-  if ((long long)npairs * chunks > (long long)INT_MAX) return fail(p, ORBX_E_INVALID, who + "too many workgroups");
+  int chunks;
+  if (const char* e = grid_problem(0, nullptr, npairs, qcap, &chunks)) return fail(p, ORBX_E_INVALID, who + e);
   int rc = same_device(p, who.c_str(), {d_best_idx12, d_best_dist12, d_nfound12, d_best_idx21, d_best_dist21, d_nfound21, d_n1, d_n2, d_match12, d_nfound},
                        "the handle");
   if (rc != ORBX_OK) return rc;

@@ -5,13 +5,13 @@ FuseBatch read, so `last(...).rows`, `reloc(...).rows` and `fuse(...).rows` go i
 runs in the HIP kernels of the library (or, for the `reference_*` functions, in its plain C++ host twins); this file only marshals buffers."""
 from __future__ import annotations
 
-from dataclasses import dataclass
 from typing import Optional
 
 import numpy as np
 
-from . import _lib, frustum
-from ._lib import OrbxError, addr, host_array as arr, host_view, ptr
+from . import _lib
+from ._front import FrontHandle, ProjectResult, _fail, _host_call, _new, _sf, level_thresholds  # noqa: F401  (what sim3 shares)
+from ._lib import addr, host_array as arr, ptr
 from .frustum import LOG_DOUBLE, LOG_FLOAT, MAX_LEVELS, SUM_LTR, SUM_TREE, TABLE_DTYPE  # noqa: F401  (the table and the options of §24)
 from .fuse import QUERY_DTYPE
 from .lastmatch import POINT_DTYPE as LAST_POINT_DTYPE
@@ -24,61 +24,14 @@ SLOT_DTYPE = np.dtype([("point", "<i4"), ("octave", "<i4"), ("angle", "<f4"), ("
 assert ITEM_DTYPE.itemsize == 128 and SLOT_DTYPE.itemsize == 16
 
 
-@dataclass
-class ProjectResult:
-    """rows [B, mcap] records of the consumer's dtype (from the device forms: a [B, mcap, 32] uint8 torch tensor on the device) and nvalid [B]
-    int32 (-1 for a malformed item)."""
-    rows: object
-    nvalid: object
-    dtype: np.dtype
-
-    def host(self) -> "ProjectResult":
-        """The same on the host: rows as a [B, mcap] array of the consumer's dtype."""
-        rows = host_view(self.rows)
-        if rows.dtype != self.dtype:
-            rows = np.ascontiguousarray(rows).view(self.dtype).reshape(rows.shape[0], rows.shape[1])
-        return ProjectResult(rows, host_view(self.nvalid), self.dtype)
-
-
-_thresholds = {}
-
-
-def level_thresholds(log_scale_factor: float, nlevels: int, log_kind: int = LOG_DOUBLE) -> np.ndarray:
-    """frustum.level_thresholds, computed once per (log_scale_factor, nlevels, log_kind): the library itself never bisects."""
-    key = (np.float32(log_scale_factor).tobytes(), int(nlevels), int(log_kind))
-    if key not in _thresholds:
-        T = frustum.level_thresholds(log_scale_factor, nlevels, log_kind)
-        T.setflags(write=False)
-        _thresholds[key] = T
-    return _thresholds[key]
-
-
-def _host_call(points, items, slots, nslots, slot_dtype):
-    points = np.ascontiguousarray(points, TABLE_DTYPE).ravel()
-    items = np.ascontiguousarray(items, ITEM_DTYPE).ravel()
-    slots = np.ascontiguousarray(slots, slot_dtype)
-    B, Q = slots.shape
-    assert len(items) == B
-    return points, items, slots, arr(nslots, np.int32, B), B, Q
-
-
-def _fail(M, rc):
-    if rc < 0:
-        raise OrbxError(rc, (M.orbx_project_last_error(None) or b"").decode())
-
-
-def _sf(scale_factors, nlevels: int) -> np.ndarray:
-    return arr(scale_factors, np.float32, int(nlevels))
-
-
 def reference_last(points, obs, items, slots, nslots, rot_kind: int = ROT_MATRIX, sum_order: int = SUM_LTR) -> ProjectResult:
     """orbx_project_last_reference: the host twin on numpy arrays (no device)."""
     M = _lib.project_lib()
-    points, items, slots, nslots, B, Q = _host_call(points, items, slots, nslots, SLOT_DTYPE)
+    points, items, slots, nslots, B, Q = _host_call(points, items, slots, nslots, ITEM_DTYPE, SLOT_DTYPE)
     obs = arr(obs, np.int32, len(points))
-    out = ProjectResult(np.zeros((B, Q), LAST_POINT_DTYPE), np.zeros(B, np.int32), LAST_POINT_DTYPE)
-    _fail(M, M.orbx_project_last_reference(ptr(points), ptr(obs), len(points), ptr(items), B, ptr(slots), ptr(nslots), Q, int(rot_kind),
-                                           int(sum_order), ptr(out.rows), ptr(out.nvalid)))
+    out = _new(B, Q, LAST_POINT_DTYPE)
+    _fail(M.orbx_project_last_error, M.orbx_project_last_reference(ptr(points), ptr(obs), len(points), ptr(items), B, ptr(slots), ptr(nslots), Q,
+                                                                   int(rot_kind), int(sum_order), ptr(out.rows), ptr(out.nvalid)))
     return out
 
 
@@ -86,10 +39,11 @@ def reference_reloc(points, items, slots, nslots, log_scale_factor: float, nleve
                     sum_order: int = SUM_LTR) -> ProjectResult:
     """orbx_project_reloc_reference: the host twin on numpy arrays (libm's log for every point, no thresholds, no device)."""
     M = _lib.project_lib()
-    points, items, slots, nslots, B, Q = _host_call(points, items, slots, nslots, SLOT_DTYPE)
-    out = ProjectResult(np.zeros((B, Q), RELOC_POINT_DTYPE), np.zeros(B, np.int32), RELOC_POINT_DTYPE)
-    _fail(M, M.orbx_project_reloc_reference(ptr(points), len(points), ptr(items), B, ptr(slots), ptr(nslots), Q, float(log_scale_factor),
-                                            int(nlevels), int(log_kind), int(rot_kind), int(sum_order), ptr(out.rows), ptr(out.nvalid)))
+    points, items, slots, nslots, B, Q = _host_call(points, items, slots, nslots, ITEM_DTYPE, SLOT_DTYPE)
+    out = _new(B, Q, RELOC_POINT_DTYPE)
+    _fail(M.orbx_project_last_error, M.orbx_project_reloc_reference(ptr(points), len(points), ptr(items), B, ptr(slots), ptr(nslots), Q,
+                                                                    float(log_scale_factor), int(nlevels), int(log_kind), int(rot_kind),
+                                                                    int(sum_order), ptr(out.rows), ptr(out.nvalid)))
     return out
 
 
@@ -97,15 +51,16 @@ def reference_fuse(points, items, idx, nslots, log_scale_factor: float, scale_fa
                    sum_order: int = SUM_LTR) -> ProjectResult:
     """orbx_project_fuse_reference: the host twin on numpy arrays; nlevels is len(scale_factors)."""
     M = _lib.project_lib()
-    points, items, idx, nslots, B, Q = _host_call(points, items, idx, nslots, np.int32)
-    sf = _sf(scale_factors, len(scale_factors))
-    out = ProjectResult(np.zeros((B, Q), QUERY_DTYPE), np.zeros(B, np.int32), QUERY_DTYPE)
-    _fail(M, M.orbx_project_fuse_reference(ptr(points), len(points), ptr(items), B, ptr(idx), ptr(nslots), Q, float(log_scale_factor), ptr(sf),
-                                           len(sf), int(log_kind), int(rot_kind), int(sum_order), ptr(out.rows), ptr(out.nvalid)))
+    points, items, idx, nslots, B, Q = _host_call(points, items, idx, nslots, ITEM_DTYPE)
+    sf = _sf(scale_factors)
+    out = _new(B, Q, QUERY_DTYPE)
+    _fail(M.orbx_project_last_error, M.orbx_project_fuse_reference(ptr(points), len(points), ptr(items), B, ptr(idx), ptr(nslots), Q,
+                                                                   float(log_scale_factor), ptr(sf), len(sf), int(log_kind), int(rot_kind),
+                                                                   int(sum_order), ptr(out.rows), ptr(out.nvalid)))
     return out
 
 
-class ProjectBatch(_lib.SideHandle):
+class ProjectBatch(FrontHandle):
     """The projection fronts of TrackWithMotionModel, Relocalization and SearchInNeighbors for batches of (pose, point list) items; one
     handle holds one stream on one GPU."""
 
@@ -113,18 +68,6 @@ class ProjectBatch(_lib.SideHandle):
         self._M = _lib.project_lib(library_path) if library_path else _lib.project_lib()
         self.device_id = int(device_id)
         super().__init__(self._M, "orbx_project", int(device_id))
-
-    def _out(self, out, like, B, Q, dtype):
-        if out is not None:
-            return out
-        import torch
-        dev = like.device if hasattr(like, "device") else torch.device("cuda", self.device_id)
-        return ProjectResult(torch.empty((B, Q, 32), dtype=torch.uint8, device=dev), torch.empty(B, dtype=torch.int32, device=dev), dtype)
-
-    @staticmethod
-    def _shape(points, slots, npoints, nitems, mcap):
-        return (int(points.shape[0]) if npoints is None else int(npoints), int(slots.shape[0]) if nitems is None else int(nitems),
-                int(slots.shape[1]) if mcap is None else int(mcap))
 
     # ---- device forms: asynchronous on `stream` (None or 0: the handle's own); without `out` the results are allocated on the slots' device
     def last(self, points, obs, items, slots, nslots, rot_kind: int = ROT_MATRIX, sum_order: int = SUM_LTR, stream=None,
@@ -159,7 +102,7 @@ class ProjectBatch(_lib.SideHandle):
         """orbx_project_fuse_device: `idx` [B, mcap] int32 on the device, `scale_factors` a host array of nlevels floats.  rows: what
         FuseBatch.search_device takes as `query`."""
         M, B, Q = self._shape(points, idx, npoints, nitems, mcap)
-        sf = _sf(scale_factors, len(scale_factors))
+        sf = _sf(scale_factors)
         T = level_thresholds(log_scale_factor, len(sf), log_kind)
         out = self._out(out, idx, B, Q, QUERY_DTYPE)
         self._check(self._M.orbx_project_fuse_device(self._h, ptr(addr(points)), M, ptr(addr(items)), B, ptr(addr(idx)), ptr(addr(nslots)), Q,
@@ -170,9 +113,9 @@ class ProjectBatch(_lib.SideHandle):
     # ---- host-array forms: numpy arrays of the same layout; they return when the results are on the host
     def last_host(self, points, obs, items, slots, nslots, rot_kind: int = ROT_MATRIX, sum_order: int = SUM_LTR) -> ProjectResult:
         """orbx_project_last."""
-        points, items, slots, nslots, B, Q = _host_call(points, items, slots, nslots, SLOT_DTYPE)
+        points, items, slots, nslots, B, Q = _host_call(points, items, slots, nslots, ITEM_DTYPE, SLOT_DTYPE)
         obs = arr(obs, np.int32, len(points))
-        out = ProjectResult(np.zeros((B, Q), LAST_POINT_DTYPE), np.zeros(B, np.int32), LAST_POINT_DTYPE)
+        out = _new(B, Q, LAST_POINT_DTYPE)
         self._check(self._M.orbx_project_last(self._h, ptr(points), ptr(obs), len(points), ptr(items), B, ptr(slots), ptr(nslots), Q, int(rot_kind),
                                               int(sum_order), ptr(out.rows), ptr(out.nvalid)))
         return out
@@ -180,9 +123,9 @@ class ProjectBatch(_lib.SideHandle):
     def reloc_host(self, points, items, slots, nslots, log_scale_factor: float, nlevels: int, log_kind: int = LOG_DOUBLE,
                    rot_kind: int = ROT_MATRIX, sum_order: int = SUM_LTR) -> ProjectResult:
         """orbx_project_reloc."""
-        points, items, slots, nslots, B, Q = _host_call(points, items, slots, nslots, SLOT_DTYPE)
+        points, items, slots, nslots, B, Q = _host_call(points, items, slots, nslots, ITEM_DTYPE, SLOT_DTYPE)
         T = level_thresholds(log_scale_factor, nlevels, log_kind)
-        out = ProjectResult(np.zeros((B, Q), RELOC_POINT_DTYPE), np.zeros(B, np.int32), RELOC_POINT_DTYPE)
+        out = _new(B, Q, RELOC_POINT_DTYPE)
         self._check(self._M.orbx_project_reloc(self._h, ptr(points), len(points), ptr(items), B, ptr(slots), ptr(nslots), Q,
                                                ptr(T) if len(T) else None, int(nlevels), int(rot_kind), int(sum_order), ptr(out.rows),
                                                ptr(out.nvalid)))
@@ -191,10 +134,10 @@ class ProjectBatch(_lib.SideHandle):
     def fuse_host(self, points, items, idx, nslots, log_scale_factor: float, scale_factors, log_kind: int = LOG_DOUBLE,
                   rot_kind: int = ROT_MATRIX, sum_order: int = SUM_LTR) -> ProjectResult:
         """orbx_project_fuse."""
-        points, items, idx, nslots, B, Q = _host_call(points, items, idx, nslots, np.int32)
-        sf = _sf(scale_factors, len(scale_factors))
+        points, items, idx, nslots, B, Q = _host_call(points, items, idx, nslots, ITEM_DTYPE)
+        sf = _sf(scale_factors)
         T = level_thresholds(log_scale_factor, len(sf), log_kind)
-        out = ProjectResult(np.zeros((B, Q), QUERY_DTYPE), np.zeros(B, np.int32), QUERY_DTYPE)
+        out = _new(B, Q, QUERY_DTYPE)
         self._check(self._M.orbx_project_fuse(self._h, ptr(points), len(points), ptr(items), B, ptr(idx), ptr(nslots), Q,
                                               ptr(T) if len(T) else None, ptr(sf), len(sf), int(rot_kind), int(sum_order), ptr(out.rows),
                                               ptr(out.nvalid)))

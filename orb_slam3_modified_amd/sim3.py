@@ -13,10 +13,11 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._lib import OrbxError, addr, host_array as arr, host_view, ptr
+from ._front import FrontHandle, ProjectResult, _fail, _host_call, _new, _sf, level_thresholds  # noqa: F401
+from ._lib import addr, host_array as arr, host_view, ptr
 from .frustum import LOG_DOUBLE, LOG_FLOAT, MAX_LEVELS, SUM_LTR, SUM_TREE, TABLE_DTYPE  # noqa: F401  (the table and the options of §24)
 from .fuse import QUERY_DTYPE
-from .project import ITEM_DTYPE as POSE_ITEM_DTYPE, ROT_MATRIX, ROT_QUAT, ProjectResult, level_thresholds  # noqa: F401  (§25's item and options)
+from .project import ITEM_DTYPE as POSE_ITEM_DTYPE, ROT_MATRIX, ROT_QUAT  # noqa: F401  (§25's item and options)
 from .projmatch import POINT_DTYPE
 
 SIM3_MATRIX, SIM3_QUAT = 0, 1
@@ -38,15 +39,6 @@ class AgreeResult:
         return AgreeResult(host_view(self.match12), host_view(self.nfound))
 
 
-def _host_call(points, items, idx, nslots, item_dtype):
-    points = np.ascontiguousarray(points, TABLE_DTYPE).ravel()
-    items = np.ascontiguousarray(items, item_dtype).ravel()
-    idx = np.ascontiguousarray(idx, np.int32)
-    B, Q = idx.shape
-    assert len(items) == B
-    return points, items, idx, arr(nslots, np.int32, B), B, Q
-
-
 def _agree_call(best_idx12, best_dist12, nfound12, best_idx21, best_dist21, nfound21, n1, n2):
     i12 = np.ascontiguousarray(best_idx12, np.int32)
     P, Q = i12.shape
@@ -55,27 +47,15 @@ def _agree_call(best_idx12, best_dist12, nfound12, best_idx21, best_dist21, nfou
     return blocks, P, Q
 
 
-def _fail(M, rc):
-    if rc < 0:
-        raise OrbxError(rc, (M.orbx_sim3_last_error(None) or b"").decode())
-
-
-def _sf(scale_factors) -> np.ndarray:
-    return arr(scale_factors, np.float32, len(scale_factors))
-
-
-def _new(B, Q, dtype) -> ProjectResult:
-    return ProjectResult(np.zeros((B, Q), dtype), np.zeros(B, np.int32), dtype)
-
-
 def reference_proj(points, items, idx, nslots, log_scale_factor: float, nlevels: int, log_kind: int = LOG_DOUBLE, rot_kind: int = ROT_MATRIX,
                    sum_order: int = SUM_LTR, proj_kind: int = PROJ_DIVIDE) -> ProjectResult:
     """orbx_sim3_proj_reference: the host twin on numpy arrays (libm's log for every point, no thresholds, no device)."""
     M = _lib.sim3_lib()
     points, items, idx, nslots, B, Q = _host_call(points, items, idx, nslots, POSE_ITEM_DTYPE)
     out = _new(B, Q, POINT_DTYPE)
-    _fail(M, M.orbx_sim3_proj_reference(ptr(points), len(points), ptr(items), B, ptr(idx), ptr(nslots), Q, float(log_scale_factor), int(nlevels),
-                                        int(log_kind), int(proj_kind), int(rot_kind), int(sum_order), ptr(out.rows), ptr(out.nvalid)))
+    _fail(M.orbx_sim3_last_error, M.orbx_sim3_proj_reference(ptr(points), len(points), ptr(items), B, ptr(idx), ptr(nslots), Q, float(log_scale_factor),
+                                                             int(nlevels), int(log_kind), int(proj_kind), int(rot_kind), int(sum_order), ptr(out.rows),
+                                                             ptr(out.nvalid)))
     return out
 
 
@@ -86,8 +66,8 @@ def reference_fuse(points, items, idx, nslots, log_scale_factor: float, scale_fa
     points, items, idx, nslots, B, Q = _host_call(points, items, idx, nslots, POSE_ITEM_DTYPE)
     sf = _sf(scale_factors)
     out = _new(B, Q, QUERY_DTYPE)
-    _fail(M, M.orbx_sim3_fuse_reference(ptr(points), len(points), ptr(items), B, ptr(idx), ptr(nslots), Q, float(log_scale_factor), ptr(sf), len(sf),
-                                        int(log_kind), int(rot_kind), int(sum_order), ptr(out.rows), ptr(out.nvalid)))
+    _fail(M.orbx_sim3_last_error, M.orbx_sim3_fuse_reference(ptr(points), len(points), ptr(items), B, ptr(idx), ptr(nslots), Q, float(log_scale_factor),
+                                                             ptr(sf), len(sf), int(log_kind), int(rot_kind), int(sum_order), ptr(out.rows), ptr(out.nvalid)))
     return out
 
 
@@ -98,8 +78,9 @@ def reference_search(points, items, idx, nslots, log_scale_factor: float, scale_
     points, items, idx, nslots, B, Q = _host_call(points, items, idx, nslots, ITEM_DTYPE)
     sf = _sf(scale_factors)
     out = _new(B, Q, QUERY_DTYPE)
-    _fail(M, M.orbx_sim3_search_reference(ptr(points), len(points), ptr(items), B, ptr(idx), ptr(nslots), Q, float(log_scale_factor), ptr(sf), len(sf),
-                                          int(log_kind), int(rot_kind), int(sum_order), int(sim_kind), ptr(out.rows), ptr(out.nvalid)))
+    _fail(M.orbx_sim3_last_error, M.orbx_sim3_search_reference(ptr(points), len(points), ptr(items), B, ptr(idx), ptr(nslots), Q, float(log_scale_factor),
+                                                               ptr(sf), len(sf), int(log_kind), int(rot_kind), int(sum_order), int(sim_kind), ptr(out.rows),
+                                                               ptr(out.nvalid)))
     return out
 
 
@@ -108,11 +89,11 @@ def reference_agree(best_idx12, best_dist12, nfound12, best_idx21, best_dist21, 
     M = _lib.sim3_lib()
     blocks, P, Q = _agree_call(best_idx12, best_dist12, nfound12, best_idx21, best_dist21, nfound21, n1, n2)
     out = AgreeResult(np.zeros((P, Q), np.int32), np.zeros(P, np.int32))
-    _fail(M, M.orbx_sim3_agree_reference(*(ptr(b) for b in blocks), P, Q, int(th_high), ptr(out.match12), ptr(out.nfound)))
+    _fail(M.orbx_sim3_last_error, M.orbx_sim3_agree_reference(*(ptr(b) for b in blocks), P, Q, int(th_high), ptr(out.match12), ptr(out.nfound)))
     return out
 
 
-class Sim3Batch(_lib.SideHandle):
+class Sim3Batch(FrontHandle):
     """The projection fronts of LoopClosing's matcher calls for batches of (pose or similarity, point list) items, and SearchBySim3's
     agreement pass; one handle holds one stream on one GPU."""
 
@@ -120,22 +101,6 @@ class Sim3Batch(_lib.SideHandle):
         self._M = _lib.sim3_lib(library_path) if library_path else _lib.sim3_lib()
         self.device_id = int(device_id)
         super().__init__(self._M, "orbx_sim3", int(device_id))
-
-    def _dev(self, like):
-        import torch
-        return like.device if hasattr(like, "device") else torch.device("cuda", self.device_id)
-
-    def _out(self, out, like, B, Q, dtype):
-        if out is not None:
-            return out
-        import torch
-        dev = self._dev(like)
-        return ProjectResult(torch.empty((B, Q, 32), dtype=torch.uint8, device=dev), torch.empty(B, dtype=torch.int32, device=dev), dtype)
-
-    @staticmethod
-    def _shape(points, idx, npoints, nitems, mcap):
-        return (int(points.shape[0]) if npoints is None else int(npoints), int(idx.shape[0]) if nitems is None else int(nitems),
-                int(idx.shape[1]) if mcap is None else int(mcap))
 
     # ---- device forms: asynchronous on `stream` (None or 0: the handle's own); without `out` the results are allocated on the indices' device
     def proj(self, points, items, idx, nslots, log_scale_factor: float, nlevels: int, log_kind: int = LOG_DOUBLE, rot_kind: int = ROT_MATRIX,

@@ -34,7 +34,7 @@ def test_build_produces_the_sim3_library():
     assert os.path.dirname(build.SIM3_OUT) == os.path.dirname(_lib.LIB_PATH) == os.path.join(ROOT, "orb_slam3_modified_amd")
     assert os.path.basename(build.SIM3_OUT) == "liborbx_sim3.so" and HEADER in build.HEADERS
     rec = [l for l in build.LIBS if l.out == build.SIM3_OUT]
-    assert len(rec) == 1 and rec[0].sources == (build.SIM3_SOURCE,) and rec[0].hidden and not rec[0].product and not rec[0].deps
+    assert len(rec) == 1 and rec[0].sources == (build.SIM3_SOURCE,) and rec[0].hidden and not rec[0].product and rec[0].deps == build.FRONT_CORE
     assert "-ffp-contract=off" in build.FLAGS                      # no product and sum, and no product and difference, is fused
     assert not [f for f in build.FLAGS if "fast" in f or "correctly-rounded" in f or "unsafe" in f or "denormal" in f], build.FLAGS
 
@@ -70,8 +70,9 @@ def test_every_other_library_keeps_its_abi_and_the_product_its_kernels():
     assert "side/orbx_handle.h" in src and "orbx_internal.h" not in src and "orbx_project.hip" not in re.sub(r"//.*", "", src)
     code = re.sub(r"//.*", "", src)
     assert "asm" not in code and not re.search(r"atomic\w*\s*\(\s*\(?\s*(float|double)", code) and "__shared__" not in code
-    # one statement of each emitter: the kernel and the option combinations of the host twin; no log on the device; no bisection here
-    assert code.count("emit_pose<") == 5 and code.count("emit_search<") == 9 and code.count("agree_one(") == 3
+    # one statement of each emitter: the kernel and the host twin, whose option combinations the front core's dispatch instantiates; no log
+    # on the device; no bisection here
+    assert code.count("emit_pose<") == 2 and code.count("emit_search<") == 2 and code.count("dispatch(") == 2 and code.count("agree_one(") == 3
     assert "log(" not in code[code.index("__global__"):] and "level_thresholds" not in code
 
 
@@ -189,8 +190,11 @@ def test_bad_thresholds_are_rejected_before_any_device_call():
         body = src[src.index("int %s(" % form):]
         body = body[:body.index("\n}\n")]
         assert body.index("thresholds_problem(") < body.index("return emit_"), form          # before the staging and the launch
-    assert src.count("thresholds_problem(") == 7                  # the definition and the six forms that take thresholds
-    text = src[src.index("const char* thresholds_problem("):]
+    assert src.count("thresholds_problem(") == 6                  # the six forms that take thresholds; the definition is the front core's
+    assert "const char* thresholds_problem(" not in src and '#include "../side/orbx_front_host.h"' in src
+    core = open(os.path.join(ROOT, "orb_slam3_modified_amd", "csrc", "side", "orbx_front_host.h")).read()
+    assert core.count("const char* thresholds_problem(") == 1
+    text = core[core.index("const char* thresholds_problem("):]
     text = text[:text.index("\n}\n")]
     for reason in ("null thresholds", "finite and positive", "strictly increasing", "levels_problem"):
         assert reason in text, reason
