@@ -10,7 +10,7 @@
  * mvpMapPoints as indices.
  * Out of scope:
  *   the pose and camera-model arithmetic of :1686-1718, bForward / bBackward included: the caller passes them as `direction`;
- *   the two-camera block (:1794-1880).
+ *   the two-camera block (:1794-1880): with Nleft != -1 the whole routine is include/orbx_rigmatch.h's (liborbx_rigmatch.so).
  *
  * The specification is the reference's loop.  For item b = {frame, direction, mbf, th}, the item's points in index order:
  *   1. a point with valid == 0 is skipped.  The caller folds `pMP`, !mvbOutlier[i], invzc >= 0 and the image-bounds tests (:1697-1718)

@@ -8,7 +8,7 @@
  * mnTrackScaleLevel: the window, the level range, the stereo gate, the Hamming best / second, the acceptance and the frame's updated
  * mvpMapPoints as indices.
  * Out of scope:
- *   the two-camera block (:143-210);
+ *   the two-camera block (:143-210): with Nleft != -1 the whole routine is include/orbx_rigmatch.h's (liborbx_rigmatch.so);
  *   the projection that produces those members (Frame::isInFrustum): the caller's Eigen and libm work;
  *   SearchByProjection(Frame, LastFrame) (:1676): the frame-to-last-frame form is include/orbx_lastmatch.h's (liborbx_lastmatch.so).
  *

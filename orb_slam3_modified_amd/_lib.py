@@ -32,6 +32,7 @@ PLACEINDEX_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_placeinde
 FRUSTUM_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_frustum.so")         # the batched Frame::isInFrustum (include/orbx_frustum.h)
 PROJECT_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_project.so")         # the LastFrame, relocalization and Fuse projections (include/orbx_project.h)
 SIM3_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_sim3.so")               # LoopClosing's Sim3 projections and agreement pass (include/orbx_sim3.h)
+RIGMATCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_rigmatch.so")       # the two-camera rig blocks of the two Tracking matchers (include/orbx_rigmatch.h)
 
 ORBX_OK, ORBX_E_INVALID, ORBX_E_EMPTY, ORBX_E_DEVICE, ORBX_E_CAPACITY, ORBX_E_FORMAT = 0, -1, -2, -3, -4, -5
 NUM_KERNELS = 6
@@ -601,10 +602,35 @@ def sim3_lib(path: str = SIM3_LIB_PATH) -> C.CDLL:
     return M
 
 
+class OrbxRigMatchSide(C.Structure):
+    """orbx_rigmatch_side (include/orbx_rigmatch.h)."""
+    _fields_ = [("d_kps_l", C.c_void_p), ("d_desc_l", C.c_void_p), ("d_counts_l", C.c_void_p), ("d_kps_r", C.c_void_p), ("d_desc_r", C.c_void_p),
+                ("d_counts_r", C.c_void_p), ("d_l2r", C.c_void_p), ("d_r2l", C.c_void_p), ("d_bounds", C.c_void_p), ("nframes", C.c_int),
+                ("cap_l", C.c_int), ("cap_r", C.c_int)]
+
+
+def rigmatch_lib(path: str = RIGMATCH_LIB_PATH) -> C.CDLL:
+    """liborbx_rigmatch.so.  `_orbx_rigmatch_symbols`: every name of include/orbx_rigmatch.h, bound here with its signature.  `path`: a
+    timing build of the same source."""
+    vp, i32, f32, sp, fp = C.c_void_p, C.c_int, C.c_float, C.POINTER(OrbxRigMatchSide), C.POINTER(C.c_float)
+    sig = {
+        "orbx_rigmatch_create": (i32, [C.POINTER(vp), i32]),
+        "orbx_rigmatch_destroy": (None, [vp]),
+        "orbx_rigmatch_last_error": (C.c_char_p, [vp]),
+        "orbx_rigmatch_local_device": (i32, [vp, sp, vp, i32, vp, vp, i32, vp, i32, fp, i32, f32, f32, vp, vp, vp, vp]),
+        "orbx_rigmatch_local": (i32, [vp, sp, vp, i32, vp, vp, i32, vp, i32, fp, i32, f32, f32, vp, vp, vp]),
+        "orbx_rigmatch_last_device": (i32, [vp, sp, vp, i32, vp, vp, i32, vp, i32, fp, i32, i32, vp, vp, vp, vp]),
+        "orbx_rigmatch_last": (i32, [vp, sp, vp, i32, vp, vp, i32, vp, i32, fp, i32, i32, vp, vp, vp]),
+    }
+    M = _load_side(path, sig)
+    M._orbx_rigmatch_symbols = tuple(sig)
+    return M
+
+
 class SideHandle:
     """A handle of a side library whose entry points are <prefix>_create / _destroy / _last_error (StereoBatch, BowBatch, MatchBatch,
     InitMatchBatch, TriMatchBatch, FuseBatch, DistinctBatch, ScoreBatch, FisheyeBatch, LocalMatchBatch, LastMatchBatch, ProjMatchBatch,
-    PlaceBatch, PlaceIndex, FrustumBatch, ProjectBatch, Sim3Batch)."""
+    PlaceBatch, PlaceIndex, FrustumBatch, ProjectBatch, Sim3Batch, RigMatchBatch)."""
 
     def __init__(self, library: C.CDLL, prefix: str, *create_args):
         self._L, self._prefix, self._h = library, prefix, C.c_void_p(0)

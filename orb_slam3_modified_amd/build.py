@@ -26,6 +26,8 @@ LIBS is the one place that knows them, one record per library; what is stale, wh
                         matchers' rows (include/orbx_project.h); takes nothing from the product
   liborbx_sim3.so       the projection fronts of LoopClosing's Sim3 callers and SearchBySim3's agreement pass (include/orbx_sim3.h);
                         takes nothing from the product
+  liborbx_rigmatch.so   the two-camera rig blocks of SearchLocalPoints and SearchByProjection(Frame, LastFrame), batched
+                        (include/orbx_rigmatch.h)
 The libraries beside the product link liborbx.so and use its ABI (and orbx_internal.h where they read a context's buffers).  Their sources sit
 in subdirectories of csrc/, outside kernels_hash(): the committed counter files measure the product's kernels, which they do not change.
 A new one is one more record ("Adding a side library")."""
@@ -80,6 +82,8 @@ PROJECT_OUT = os.path.join(os.path.dirname(OUT), "liborbx_project.so")
 PROJECT_SOURCE = os.path.join("project", "orbx_project.hip")
 SIM3_OUT = os.path.join(os.path.dirname(OUT), "liborbx_sim3.so")
 SIM3_SOURCE = os.path.join("sim3", "orbx_sim3.hip")
+RIGMATCH_OUT = os.path.join(os.path.dirname(OUT), "liborbx_rigmatch.so")
+RIGMATCH_SOURCE = os.path.join("rigmatch", "orbx_rigmatch.hip")
 FRONT_CORE = (os.path.join("side", "orbx_front_device.h"), os.path.join("side", "orbx_front_host.h"))   # what the three projection fronts share
 
 
@@ -110,10 +114,11 @@ LIBS = (Lib(OUT, tuple(SOURCES)),
         Lib(PLACEINDEX_OUT, (PLACEINDEX_SOURCE,), hidden=True, deps=(PLACE_KERNELS,)),
         Lib(FRUSTUM_OUT, (FRUSTUM_SOURCE,), hidden=True, deps=FRONT_CORE),
         Lib(PROJECT_OUT, (PROJECT_SOURCE,), hidden=True, deps=FRONT_CORE),
-        Lib(SIM3_OUT, (SIM3_SOURCE,), hidden=True, deps=FRONT_CORE))
+        Lib(SIM3_OUT, (SIM3_SOURCE,), hidden=True, deps=FRONT_CORE),
+        Lib(RIGMATCH_OUT, (RIGMATCH_SOURCE,), hidden=True, deps=WINDOW_CORE))
 HEADERS = ("orbx.h", "orbx_debug.h", "orbx_train.h", "orbx_stereo.h", "orbx_bow.h", "orbx_match.h", "orbx_initmatch.h", "orbx_trimatch.h",
            "orbx_fuse.h", "orbx_mpdesc.h", "orbx_score.h", "orbx_fisheye.h", "orbx_localmatch.h", "orbx_lastmatch.h",
-           "orbx_projmatch.h", "orbx_place.h", "orbx_placeindex.h", "orbx_frustum.h", "orbx_project.h", "orbx_sim3.h")
+           "orbx_projmatch.h", "orbx_place.h", "orbx_placeindex.h", "orbx_frustum.h", "orbx_project.h", "orbx_sim3.h", "orbx_rigmatch.h")
 # -ffp-contract=off: the float paths (fastAtan2 polynomial, BRIEF rotation) must not be fused into FMAs,
 # the CPU reference evaluates them as separate IEEE operations (DESIGN.md "bit-exactness").
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall",
