@@ -70,7 +70,7 @@ LASTMATCH_OUT = os.path.join(os.path.dirname(OUT), "liborbx_lastmatch.so")
 LASTMATCH_SOURCE = os.path.join("lastmatch", "orbx_lastmatch.hip")
 PROJMATCH_OUT = os.path.join(os.path.dirname(OUT), "liborbx_projmatch.so")
 PROJMATCH_SOURCE = os.path.join("projmatch", "orbx_projmatch.hip")
-WINDOW_CORE = (os.path.join("side", "orbx_window_device.h"), os.path.join("side", "orbx_window_host.h"))   # what those three share
+WINDOW_CORE = (os.path.join("side", "orbx_window_device.h"), os.path.join("side", "orbx_window_host.h"))   # what those three and the rig matcher share
 PLACE_OUT = os.path.join(os.path.dirname(OUT), "liborbx_place.so")
 PLACE_SOURCE = os.path.join("place", "orbx_place.hip")
 PLACE_KERNELS = os.path.join("place", "orbx_place_kernels.h")   # what the two place libraries share

@@ -3,24 +3,22 @@
 // descriptors a batch extraction left in HBM and the points' descriptors in the pool ComputeDistinctiveDescriptors fills.
 //
 // k_last_match<LDS>: one workgroup of 8 waves per item (a grid of at most kMaxBlocks workgroups walks the items).  The frame grid, the
-// window walk, the offsets' scan, the chunk cut, the rotation filter and the two paths' layout are csrc/side/orbx_window_device.h's; this
-// file holds what is this matcher's own:
+// window walk, the offsets' scan, the chunk cut, the chain's step (the scan over the open candidates, the bind), the last writer, the
+// rotation filter and the two paths' layout are csrc/side/orbx_window_device.h's; this file holds what is this matcher's own:
 //   check                the item's frame, count, nlast, direction and th and every valid point's octave and pool row, before any of them
 //                        addresses memory.
 //   phase A              the window GetFeaturesInArea(u, v, radius, the direction's level range) with the stereo gate; a candidate is one
 //                        word: index (15 bits), Hamming distance (9).  The kp_obs test is the chain's.  (Only a best is kept, so entries
 //                        above 100 could be left out of the lists; they are not: leaving them out would need the distances in the counting
 //                        walk too, and the chain passes over them in the same trip.)
-//   phase B, wave 0      the chain over the chunk's points in index order: lane j holds candidate j (+ 64 per trip), drops the entries whose
-//                        keypoint is hidden (a bit per keypoint in LDS, from the kp_obs row, set on every acceptance with obs > 0), keeps its
-//                        smallest (distance << 15 | position) key; one DPP min-reduction gives the wave's smallest: the first in walk order
-//                        among equal distances.  The accept test is wave-uniform; one lane records the point's keypoint and sets the hidden
-//                        bit.  No descriptor and no keypoint is read here.  A and B repeat per chunk: the distances do not depend on the
-//                        chain, so where the chunks are cut changes nothing.
-//   phase C, all waves   kp_match[keypoint] = the LAST accepted point that took it (an integer maximum over the points' indices), then
-//                        kp_obs[keypoint] = that point's obs.
-//   phase D, all waves   under check_orientation, the rotation filter: every entry of a bin outside the three maxima writes kp_match = -2,
-//                        kp_obs = -1: entries of one keypoint write the same values, so nothing depends on the order.
+//   phase B, wave 0      the walk over the chunk's points in index order; a step is the core's on the smallest key of the candidates whose
+//                        keypoint is not hidden (a bit per keypoint in LDS, from the kp_obs row, set on every acceptance with obs > 0): the
+//                        first in walk order among equal distances, accepted at a distance of at most 100 (:1770).  The accept test is
+//                        wave-uniform.  No descriptor and no keypoint is read here.  A and B repeat per chunk: the distances do not depend
+//                        on the chain, so where the chunks are cut changes nothing.
+//   phase C, all waves   the core's last writer.
+//   phase D, all waves   under check_orientation, the core's rotation filter: every entry of a bin outside the three maxima writes
+//                        kp_match = -2, kp_obs = -1: entries of one keypoint write the same values, so nothing depends on the order.
 // The hidden bits are 4 KiB of static LDS on both paths.
 // The float expressions are compiled with -ffp-contract=off: every operation is rounded by itself, as the specification states them.
 #include <hip/hip_runtime.h>
@@ -38,10 +36,9 @@ struct orbx_lastmatch : orbx::side::win::WindowHandle {};   // lds_limit: ORBX_L
 namespace {
 
 using namespace orbx::side;
-using namespace orbx::side::dev;          // ld / st on the chain's state: written by one lane, read by the wave's other lanes in the next step
+using namespace orbx::side::dev;
 using namespace orbx::side::win;
 
-constexpr int kThHigh = 100;
 static_assert(ORBX_LASTMATCH_MAX_CAPACITY == kMaxCap && ORBX_LASTMATCH_MAX_LEVELS == kMaxLevels, "the window core's limits");
 
 struct Args {
@@ -90,7 +87,7 @@ __global__ __launch_bounds__(kThreads) void k_last_match(Args g) {
   const int cap = g.cap, mcap = g.mcap;
   const Lay L = layout(cap, mcap, g.p2, LDS);
   uint8_t* const base = LDS ? smem : g.scratch + (size_t)blockIdx.x * g.scratch_stride;
-  const Arrays A = arrays(base, L);
+  const Arrays A = arrays(base, L, L.grid);
   int32_t *const offs = A.offs, *const res = A.res;
   uint32_t* const cand = A.cand;
   load_levels(s_sf, g.sf);
@@ -189,23 +186,12 @@ __global__ __launch_bounds__(kThreads) void k_last_match(Args g) {
             const int cnt = __builtin_amdgcn_readlane(l_n, i);
             if (cnt <= 0) continue;
             const int b0 = __builtin_amdgcn_readlane(l_b, i);
-            int k1 = kNone;                // the lane's smallest (distance << 15 | position)
-            for (int j = lane; j < cnt; j += 64) {
-              const uint32_t e = cand[b0 + j];
-              const int idx = (int)(e & 0x7FFFu);
-              if ((ld(s_hidden + (idx >> 5)) >> (idx & 31)) & 1) continue;
-              k1 = min(k1, (int)((e >> 15) & 0x1FFu) << 15 | j);
-            }
-            const int m1 = wave_min(k1);
+            const int m1 = open_top(cand, b0, cnt, 0, s_hidden, lane);
             if (m1 == kNone || (m1 >> 15) > kThHigh) continue;   // :1770
             const int obs = __builtin_amdgcn_readlane(l_obs, i);
-            if (lane == 0) {
-              const int idx = (int)(cand[b0 + (m1 & 0x7FFF)] & 0x7FFFu);
-              st(res + c0 + i, idx);
-              if (obs > 0) st(s_hidden + (idx >> 5), ld(s_hidden + (idx >> 5)) | (int)(1u << (idx & 31)));
-            }
+            if (lane == 0) bind<false>(s_hidden, res + c0 + i, (int)(cand[b0 + (m1 & 0x7FFF)] & 0x7FFFu), obs);   // the slot was open: obs <= 0 leaves its bit clear
             nm++;
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // the stores are done before the next point's loads
+            publish();
           }
         }
       }
@@ -214,21 +200,13 @@ __global__ __launch_bounds__(kThreads) void k_last_match(Args g) {
       q0 = q1;
     }
 
-    // ---- phase C: the last point that took a keypoint holds it; integer maxima, so the order does not matter
-    for (int q = tid; q < nlast; q += kThreads) {
-      const int i = res[q];
-      if (i >= 0 && i < n) __hip_atomic_fetch_max(omatch + i, q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    for (int i = tid; i < n; i += kThreads) {
-      const int q = __hip_atomic_load(omatch + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (q >= 0 && q < nlast) oobs[i] = pts[q].obs;
-    }
+    last_writer<kThreads, 1>(res, nlast, n, omatch, oobs, [&](int q) { return pts[q].obs; });   // ---- phase C
     int removed = 0;
 #ifndef ORBX_LASTMATCH_NO_HIST             // (a timing build without phase D: tools/lastmatch_times.py)
     // ---- phase D: the rotation histogram (:1775-1792), its three maxima and the removal (:1862-1882)
     if (g.check_ori)                       // uniform over the grid; its first barrier: phase C's reads of kp_match and writes of kp_obs are done
-      removed = rotation_filter<kThreads>(res, nlast, n, kp, [&](int q) { return pts[q].angle; }, [&](int i) { omatch[i] = -2; oobs[i] = -1; });
+      removed = rotation_filter<kThreads, 1>(res, nlast, n, [&](int q) { return pts[q].angle; }, [&](int i) { return kp_field<float>(kp, i, kAngle); },
+                                             [&](int i) { omatch[i] = -2; oobs[i] = -1; });
 #endif
     if (tid == 0) g.nmatches[b] = nm - removed;
   }
@@ -276,15 +254,10 @@ int orbx_lastmatch_search_device(orbx_lastmatch* m, const orbx_lastmatch_side* s
   g.kps = (const uint8_t*)side->d_kps; g.desc = side->d_desc; g.counts = side->d_counts; g.uright = side->d_uright; g.bounds = side->d_bounds;
   g.items = d_items; g.pts = d_points; g.nlast = d_nlast; g.pdesc = d_pdesc;
   g.kp_obs = d_kp_obs; g.kp_match = d_kp_match; g.nmatches = d_nmatches;
-  g.scratch = path.in_lds ? nullptr : m->scratch.p; g.scratch_stride = path.scratch_stride;
-  g.nframes = side->nframes; g.cap = cap; g.nitems = nitems; g.mcap = mcap; g.npoints = npoints; g.nlevels = nlevels; g.p2 = p2; g.room = path.room;
+  g.nframes = side->nframes; g.cap = cap; g.nitems = nitems; g.mcap = mcap; g.npoints = npoints; g.nlevels = nlevels; g.p2 = p2;
   g.check_ori = check_orientation != 0;
   fill_levels(g.sf, scale_factors, nlevels);
-  hipStream_t st = stream ? (hipStream_t)stream : m->st;
-  if ((rc = wait_previous(m, st)) != ORBX_OK) return rc;
-  if (path.in_lds) hipLaunchKernelGGL(k_last_match<true>, dim3((unsigned)path.blocks), dim3(kThreads), path.lds_bytes, st, g);
-  else hipLaunchKernelGGL(k_last_match<false>, dim3((unsigned)path.blocks), dim3(kThreads), 0, st, g);
-  return record_call(m, st);
+  return launch(m, path, g, k_last_match<true>, k_last_match<false>, stream);
 }
 
 int orbx_lastmatch_search(orbx_lastmatch* m, const orbx_lastmatch_side* side, const orbx_lastmatch_item* items, int nitems,
@@ -296,17 +269,15 @@ int orbx_lastmatch_search(orbx_lastmatch* m, const orbx_lastmatch_side* side, co
   int rc = check(m, who, side, items, nitems, points, nlast, mcap, pdesc, npoints, scale_factors, nlevels, kp_obs, kp_match, nmatches);
   if (rc != ORBX_OK) return rc;
   Stager io;
-  const size_t nf = (size_t)side->nframes, nk = nf * side->capacity, rows = (size_t)nitems * side->capacity;
-  const size_t o_kps = io.in(side->d_kps, nk * sizeof(orbx_keypoint)), o_desc = io.in(side->d_desc, nk * 32), o_counts = io.in(side->d_counts, nf * 8);
-  const size_t o_ur = side->d_uright ? io.in(side->d_uright, nk * 4) : 0, o_bounds = io.in(side->d_bounds, nf * 16);
+  const size_t rows = (size_t)nitems * side->capacity;
+  const StagedSide ss = stage_side(io, side, &orbx_lastmatch_side::d_uright);
   const size_t o_items = io.in(items, (size_t)nitems * sizeof(orbx_lastmatch_item));
   const size_t o_pts = io.in(points, (size_t)nitems * mcap * sizeof(orbx_lastmatch_point));
   const size_t o_nlast = io.in(nlast, (size_t)nitems * 4), o_pdesc = io.in(pdesc, (size_t)npoints * 32);
   const size_t o_obs = io.out(kp_obs, rows * 4, true), o_match = io.out(kp_match, rows * 4), o_nm = io.out(nmatches, (size_t)nitems * 4);
   if ((rc = upload(m, io)) != ORBX_OK) return rc;
   uint8_t* const d = m->io.p;
-  const orbx_lastmatch_side ds = {(const orbx_keypoint*)(d + o_kps), d + o_desc, (const int32_t*)(d + o_counts),
-                                  side->d_uright ? (const float*)(d + o_ur) : nullptr, (const float*)(d + o_bounds), side->nframes, side->capacity};
+  const orbx_lastmatch_side ds = device_side(d, ss, side, &orbx_lastmatch_side::d_uright);
   rc = orbx_lastmatch_search_device(m, &ds, (const orbx_lastmatch_item*)(d + o_items), nitems, (const orbx_lastmatch_point*)(d + o_pts),
                                     (const int32_t*)(d + o_nlast), mcap, d + o_pdesc, npoints, scale_factors, nlevels, check_orientation,
                                     (int32_t*)(d + o_obs), (int32_t*)(d + o_match), (int32_t*)(d + o_nm), m->st);

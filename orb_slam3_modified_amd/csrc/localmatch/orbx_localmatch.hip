@@ -3,19 +3,17 @@
 // and the map points' descriptors in the pool ComputeDistinctiveDescriptors fills.
 //
 // k_local_match<LDS>: one workgroup of 8 waves per item (a grid of at most kMaxBlocks workgroups walks the items).  The frame grid, the
-// window walk, the offsets' scan, the chunk cut and the two paths' layout are csrc/side/orbx_window_device.h's; this file holds what is
-// this matcher's own:
+// window walk, the offsets' scan, the chunk cut, the chain's step (the scan over the open candidates, the ratio test, the bind), the last
+// writer and the two paths' layout are csrc/side/orbx_window_device.h's; this file holds what is this matcher's own:
 //   check                the item's frame, count, nmp and every in-view point's level and pool row, before any of them addresses memory.
 //   phase A              the window GetFeaturesInArea(x, y, radius, level - 1, level) with the stereo gate; a candidate is one word: index
 //                        (15 bits), Hamming distance (9), octave (5, two's complement: -1 .. 15).  The kp_obs test is the chain's.
-//   phase B, wave 0      the chain over the chunk's points in index order: lane j holds candidate j (+ 64 per trip), drops the entries whose
-//                        keypoint is hidden (a bit per keypoint in LDS, from the kp_obs row, set on every acceptance with obs > 0), keeps its
-//                        two smallest (distance << 15 | position) keys; two DPP min-reductions give the wave's two smallest, whose entries
-//                        carry the octaves.  The accept test is wave-uniform; one lane records the point's keypoint and sets the hidden bit.
-//                        No descriptor and no keypoint is read here.  A and B repeat per chunk: the distances do not depend on the chain,
-//                        so where the chunks are cut changes nothing.
-//   phase C, all waves   kp_match[keypoint] = the LAST accepted point that took it (an integer maximum over the points' indices: a point
-//                        with obs == 0 does not hide its keypoint, a later one may rebind it), then kp_obs[keypoint] = that point's obs.
+//   phase B, wave 0      the walk over the chunk's points in index order; a step is the core's on the two smallest keys of the candidates
+//                        whose keypoint is not hidden (a bit per keypoint in LDS, from the kp_obs row, set on every acceptance with
+//                        obs > 0): accepted on ratio_test's outcome 2 alone (:117-130; a NaN ratio accepts nothing).  The accept test is
+//                        wave-uniform.  No descriptor and no keypoint is read here.  A and B repeat per chunk: the distances do not depend
+//                        on the chain, so where the chunks are cut changes nothing.
+//   phase C, all waves   the core's last writer: a point with obs == 0 does not hide its keypoint, a later one may rebind it.
 // The hidden bits are 4 KiB of static LDS on both paths.
 // The float expressions are compiled with -ffp-contract=off: every operation is rounded by itself, as the specification states them.
 #include <hip/hip_runtime.h>
@@ -34,10 +32,9 @@ struct orbx_localmatch : orbx::side::win::WindowHandle {};   // lds_limit: ORBX_
 namespace {
 
 using namespace orbx::side;
-using namespace orbx::side::dev;          // ld / st on the chain's state: written by one lane, read by the wave's other lanes in the next step
+using namespace orbx::side::dev;
 using namespace orbx::side::win;
 
-constexpr int kThHigh = 100;
 static_assert(ORBX_LOCALMATCH_MAX_CAPACITY == kMaxCap && ORBX_LOCALMATCH_MAX_LEVELS == kMaxLevels, "the window core's limits");
 
 struct Args {
@@ -80,7 +77,7 @@ __global__ __launch_bounds__(kThreads) void k_local_match(Args g) {
   const int cap = g.cap, mcap = g.mcap;
   const Lay L = layout(cap, mcap, g.p2, LDS);
   uint8_t* const base = LDS ? smem : g.scratch + (size_t)blockIdx.x * g.scratch_stride;
-  const Arrays A = arrays(base, L);
+  const Arrays A = arrays(base, L, L.grid);
   int32_t *const offs = A.offs, *const res = A.res;
   uint32_t* const cand = A.cand;
   load_levels(s_sf, g.sf);
@@ -178,37 +175,16 @@ __global__ __launch_bounds__(kThreads) void k_local_match(Args g) {
             const int cnt = __builtin_amdgcn_readlane(l_n, i);
             if (cnt <= 0) continue;
             const int b0 = __builtin_amdgcn_readlane(l_b, i);
-            int k1 = kNone, k2 = kNone;    // the lane's two smallest (distance << 15 | position)
-            for (int j = lane; j < cnt; j += 64) {
-              const uint32_t e = cand[b0 + j];
-              const int idx = (int)(e & 0x7FFFu);
-              if ((ld(s_hidden + (idx >> 5)) >> (idx & 31)) & 1) continue;
-              const int key = (int)((e >> 15) & 0x1FFu) << 15 | j;
-              const int hi = max(k1, key);
-              k1 = min(k1, key);
-              k2 = min(k2, hi);
-            }
-            const int m1 = wave_min(k1);
-            if (m1 == kNone || (m1 >> 15) > kThHigh) continue;
-            const int m2 = wave_min(k1 == m1 ? k2 : k1);   // positions are unique: one lane holds m1
-            const uint32_t e1 = cand[b0 + (m1 & 0x7FFF)];
-            const int best = m1 >> 15, level1 = (int)(e1 >> 24 & 31u);
-            int second = 256, level2 = 31; // bestDist2 = 256, bestLevel2 = -1
-            if (m2 != kNone) {
-              second = m2 >> 15;
-              level2 = (int)(cand[b0 + (m2 & 0x7FFF)] >> 24 & 31u);
-            }
-            // :117-130: dropped when the levels agree and bestDist > mfNNratio * bestDist2, kept when they differ or bestDist <= ...
-            if (level1 != level2 || (float)best <= g.ratio * (float)second) {
-              const int obs = __builtin_amdgcn_readlane(l_obs, i);
-              if (lane == 0) {
-                const int idx = (int)(e1 & 0x7FFFu);
-                st(res + c0 + i, idx);
-                if (obs > 0) st(s_hidden + (idx >> 5), ld(s_hidden + (idx >> 5)) | (int)(1u << (idx & 31)));
-              }
-              nm++;
-              __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // the stores are done before the next point's loads
-            }
+            LaneKeys mine;
+            int idx = 0;
+            const int m1 = open_top(cand, b0, cnt, 0, s_hidden, lane, &mine);
+            if ((m1 >> 15) > kThHigh) continue;
+            const int m2 = open_second(mine, m1);
+            if (ratio_test(cand, b0, m1, m2, g.ratio, &idx) != 2) continue;   // :117-130
+            const int obs = __builtin_amdgcn_readlane(l_obs, i);
+            if (lane == 0) bind<false>(s_hidden, res + c0 + i, idx, obs);   // the slot was open: obs <= 0 leaves its bit clear
+            nm++;
+            publish();
           }
         }
       }
@@ -217,16 +193,7 @@ __global__ __launch_bounds__(kThreads) void k_local_match(Args g) {
       q0 = q1;
     }
 
-    // ---- phase C: the last point that took a keypoint holds it; integer maxima, so the order does not matter
-    for (int q = tid; q < nmp; q += kThreads) {
-      const int i = res[q];
-      if (i >= 0 && i < n) __hip_atomic_fetch_max(omatch + i, q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    for (int i = tid; i < n; i += kThreads) {
-      const int q = __hip_atomic_load(omatch + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (q >= 0 && q < nmp) oobs[i] = mp[q].obs;
-    }
+    last_writer<kThreads, 1>(res, nmp, n, omatch, oobs, [&](int q) { return mp[q].obs; });   // ---- phase C
     if (tid == 0) g.nmatches[b] = nm;
   }
 }
@@ -274,16 +241,11 @@ int orbx_localmatch_search_device(orbx_localmatch* m, const orbx_localmatch_side
   g.kps = (const uint8_t*)side->d_kps; g.desc = side->d_desc; g.counts = side->d_counts; g.uright = side->d_uright; g.bounds = side->d_bounds;
   g.frames = d_frames; g.mp = d_mp; g.nmp = d_nmp; g.pdesc = d_pdesc;
   g.kp_obs = d_kp_obs; g.kp_match = d_kp_match; g.nmatches = d_nmatches;
-  g.scratch = path.in_lds ? nullptr : m->scratch.p; g.scratch_stride = path.scratch_stride;
-  g.nframes = side->nframes; g.cap = cap; g.nitems = nitems; g.mcap = mcap; g.npoints = npoints; g.nlevels = nlevels; g.p2 = p2; g.room = path.room;
+  g.nframes = side->nframes; g.cap = cap; g.nitems = nitems; g.mcap = mcap; g.npoints = npoints; g.nlevels = nlevels; g.p2 = p2;
   g.factor = (double)th != 1.0;            // bFactor, src/ORBmatcher.cc:48
   g.th = th; g.ratio = nn_ratio;
   fill_levels(g.sf, scale_factors, nlevels);
-  hipStream_t st = stream ? (hipStream_t)stream : m->st;
-  if ((rc = wait_previous(m, st)) != ORBX_OK) return rc;
-  if (path.in_lds) hipLaunchKernelGGL(k_local_match<true>, dim3((unsigned)path.blocks), dim3(kThreads), path.lds_bytes, st, g);
-  else hipLaunchKernelGGL(k_local_match<false>, dim3((unsigned)path.blocks), dim3(kThreads), 0, st, g);
-  return record_call(m, st);
+  return launch(m, path, g, k_local_match<true>, k_local_match<false>, stream);
 }
 
 int orbx_localmatch_search(orbx_localmatch* m, const orbx_localmatch_side* side, const int32_t* frames, int nitems,
@@ -295,16 +257,14 @@ int orbx_localmatch_search(orbx_localmatch* m, const orbx_localmatch_side* side,
   int rc = check(m, who, side, frames, nitems, mp, nmp, mcap, pdesc, npoints, scale_factors, nlevels, th, kp_obs, kp_match, nmatches);
   if (rc != ORBX_OK) return rc;
   Stager io;
-  const size_t nf = (size_t)side->nframes, nk = nf * side->capacity, rows = (size_t)nitems * side->capacity;
-  const size_t o_kps = io.in(side->d_kps, nk * sizeof(orbx_keypoint)), o_desc = io.in(side->d_desc, nk * 32), o_counts = io.in(side->d_counts, nf * 8);
-  const size_t o_ur = side->d_uright ? io.in(side->d_uright, nk * 4) : 0, o_bounds = io.in(side->d_bounds, nf * 16);
+  const size_t rows = (size_t)nitems * side->capacity;
+  const StagedSide ss = stage_side(io, side, &orbx_localmatch_side::d_uright);
   const size_t o_frames = io.in(frames, (size_t)nitems * 4), o_mp = io.in(mp, (size_t)nitems * mcap * sizeof(orbx_localmatch_point));
   const size_t o_nmp = io.in(nmp, (size_t)nitems * 4), o_pdesc = io.in(pdesc, (size_t)npoints * 32);
   const size_t o_obs = io.out(kp_obs, rows * 4, true), o_match = io.out(kp_match, rows * 4), o_nm = io.out(nmatches, (size_t)nitems * 4);
   if ((rc = upload(m, io)) != ORBX_OK) return rc;
   uint8_t* const d = m->io.p;
-  const orbx_localmatch_side ds = {(const orbx_keypoint*)(d + o_kps), d + o_desc, (const int32_t*)(d + o_counts),
-                                   side->d_uright ? (const float*)(d + o_ur) : nullptr, (const float*)(d + o_bounds), side->nframes, side->capacity};
+  const orbx_localmatch_side ds = device_side(d, ss, side, &orbx_localmatch_side::d_uright);
   rc = orbx_localmatch_search_device(m, &ds, (const int32_t*)(d + o_frames), nitems, (const orbx_localmatch_point*)(d + o_mp),
                                      (const int32_t*)(d + o_nmp), mcap, d + o_pdesc, npoints, scale_factors, nlevels, th, nn_ratio,
                                      (int32_t*)(d + o_obs), (int32_t*)(d + o_match), (int32_t*)(d + o_nm), m->st);

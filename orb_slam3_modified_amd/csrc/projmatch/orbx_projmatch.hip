@@ -4,8 +4,8 @@
 // descriptors a batch extraction left in HBM and the points' descriptors in the pool ComputeDistinctiveDescriptors fills.
 //
 // k_proj_match<LDS>: one workgroup of 8 waves per item (a grid of at most kMaxBlocks workgroups walks the items).  The frame grid, the
-// window walk, the offsets' scan, the chunk cut, the rotation filter and the two paths' layout are csrc/side/orbx_window_device.h's; this
-// file holds what is this matcher's own:
+// window walk, the offsets' scan, the chunk cut, the chain's step (the scan over the open candidates, the bind), the rotation filter and
+// the two paths' layout are csrc/side/orbx_window_device.h's; this file holds what is this matcher's own:
 //   check                the item's frame, count, npts, kind and th and every valid point's level and pool row, before any of them
 //                        addresses memory.
 //   phase A              the window GetFeaturesInArea(u, v, radius, level - 1, level + 1 - kind), no stereo gate (the records' right
@@ -13,13 +13,13 @@
 //                        same keypoints in the same order.  A candidate is one word: index (15 bits), Hamming distance (9).  The taken test
 //                        is the chain's.  (Only a best is kept, so entries above the item's max_dist could be left out of the lists; they
 //                        are not: see DESIGN.md section 21.)
-//   phase B, wave 0      the chain over the chunk's points in index order: lane j holds candidate j (+ 64 per trip), drops the entries whose
-//                        keypoint is taken (a bit per keypoint in LDS, from the kp_taken row, set on every acceptance), keeps its smallest
-//                        (distance << 15 | position) key; one DPP min-reduction gives the wave's smallest: the first in walk order among
-//                        equal distances.  The accept test, a float compare against the item's max_dist, is wave-uniform; one lane writes
-//                        kp_match, records the point's keypoint and sets the bit.  No descriptor and no keypoint is read here.  A and B
-//                        repeat per chunk: the distances do not depend on the chain, so where the chunks are cut changes nothing.
-//   phase D, all waves   kind 0 under check_orientation, the rotation filter: every entry of a bin outside the three maxima writes
+//   phase B, wave 0      the walk over the chunk's points in index order; a step is the core's on the smallest key of the candidates whose
+//                        keypoint is not taken (a bit per keypoint in LDS, from the kp_taken row, set on every acceptance; :504, :1952):
+//                        the first in walk order among equal distances.  The accept test, a float compare against the item's max_dist, is
+//                        wave-uniform; the binding lane writes kp_match too: there is no phase C.  No descriptor and no keypoint is read
+//                        here.  A and B repeat per chunk: the distances do not depend on the chain, so where the chunks are cut changes
+//                        nothing.
+//   phase D, all waves   kind 0 under check_orientation, the core's rotation filter: every entry of a bin outside the three maxima writes
 //                        kp_match = -2.  A keypoint is bound at most once per row, so every entry is a keypoint of its own.
 // The taken bits are 4 KiB of static LDS on both paths.
 // The float expressions are compiled with -ffp-contract=off: every operation is rounded by itself, as the specification states them.
@@ -38,7 +38,7 @@ struct orbx_projmatch : orbx::side::win::WindowHandle {};   // lds_limit: ORBX_P
 namespace {
 
 using namespace orbx::side;
-using namespace orbx::side::dev;          // ld / st on the chain's state: written by one lane, read by the wave's other lanes in the next step
+using namespace orbx::side::dev;
 using namespace orbx::side::win;
 
 static_assert(ORBX_PROJMATCH_MAX_CAPACITY == kMaxCap && ORBX_PROJMATCH_MAX_LEVELS == kMaxLevels, "the window core's limits");
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(kThreads) void k_proj_match(Args g) {
   const int cap = g.cap, mcap = g.mcap;
   const Lay L = layout(cap, mcap, g.p2, LDS);
   uint8_t* const base = LDS ? smem : g.scratch + (size_t)blockIdx.x * g.scratch_stride;
-  const Arrays A = arrays(base, L);
+  const Arrays A = arrays(base, L, L.grid);
   int32_t *const offs = A.offs, *const res = A.res;
   uint32_t* const cand = A.cand;
   load_levels(s_sf, g.sf);
@@ -173,23 +173,15 @@ __global__ __launch_bounds__(kThreads) void k_proj_match(Args g) {
             const int cnt = __builtin_amdgcn_readlane(l_n, i);
             if (cnt <= 0) continue;
             const int b0 = __builtin_amdgcn_readlane(l_b, i);
-            int k1 = kNone;                // the lane's smallest (distance << 15 | position)
-            for (int j = lane; j < cnt; j += 64) {
-              const uint32_t e = cand[b0 + j];
-              const int idx = (int)(e & 0x7FFFu);
-              if ((ld(s_taken + (idx >> 5)) >> (idx & 31)) & 1) continue;   // :504, :1952
-              k1 = min(k1, (int)((e >> 15) & 0x1FFu) << 15 | j);
-            }
-            const int m1 = wave_min(k1);
+            const int m1 = open_top(cand, b0, cnt, 0, s_taken, lane);
             if (m1 == kNone || !((float)(m1 >> 15) <= max_dist)) continue;   // :523, :636, :1966; a NaN limit accepts nothing
             if (lane == 0) {
               const int idx = (int)(cand[b0 + (m1 & 0x7FFF)] & 0x7FFFu);     // below n: a candidate is a keypoint of the grid
               omatch[idx] = c0 + i;
-              st(res + c0 + i, idx);
-              st(s_taken + (idx >> 5), ld(s_taken + (idx >> 5)) | (int)(1u << (idx & 31)));
+              bind<false>(s_taken, res + c0 + i, idx, 1);
             }
             nm++;
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // the stores are done before the next point's loads
+            publish();
           }
         }
       }
@@ -202,7 +194,8 @@ __global__ __launch_bounds__(kThreads) void k_proj_match(Args g) {
 #ifndef ORBX_PROJMATCH_NO_HIST             // (a timing build without phase D: tools/projmatch_times.py)
     // ---- phase D: the rotation histogram (:1971-1981), its three maxima and the removal (:1988-2007); the Sim3 overloads have none
     if (g.check_ori && kind == 0)          // uniform over the workgroup; -2 after the chain's store to the same word: barriers lie between them
-      removed = rotation_filter<kThreads>(res, npts, n, kp, [&](int q) { return pts[q].angle; }, [&](int i) { omatch[i] = -2; });
+      removed = rotation_filter<kThreads, 1>(res, npts, n, [&](int q) { return pts[q].angle; }, [&](int i) { return kp_field<float>(kp, i, kAngle); },
+                                             [&](int i) { omatch[i] = -2; });
 #endif
     if (tid == 0) g.nmatches[b] = nm - removed;
   }
@@ -250,15 +243,10 @@ int orbx_projmatch_search_device(orbx_projmatch* m, const orbx_projmatch_side* s
   g.kps = (const uint8_t*)side->d_kps; g.desc = side->d_desc; g.counts = side->d_counts; g.bounds = side->d_bounds;
   g.items = d_items; g.pts = d_points; g.npts = d_npts; g.pdesc = d_pdesc;
   g.kp_taken = d_kp_taken; g.kp_match = d_kp_match; g.nmatches = d_nmatches;
-  g.scratch = path.in_lds ? nullptr : m->scratch.p; g.scratch_stride = path.scratch_stride;
-  g.nframes = side->nframes; g.cap = cap; g.nitems = nitems; g.mcap = mcap; g.npoints = npoints; g.nlevels = nlevels; g.p2 = p2; g.room = path.room;
+  g.nframes = side->nframes; g.cap = cap; g.nitems = nitems; g.mcap = mcap; g.npoints = npoints; g.nlevels = nlevels; g.p2 = p2;
   g.check_ori = check_orientation != 0;
   fill_levels(g.sf, scale_factors, nlevels);
-  hipStream_t st = stream ? (hipStream_t)stream : m->st;
-  if ((rc = wait_previous(m, st)) != ORBX_OK) return rc;
-  if (path.in_lds) hipLaunchKernelGGL(k_proj_match<true>, dim3((unsigned)path.blocks), dim3(kThreads), path.lds_bytes, st, g);
-  else hipLaunchKernelGGL(k_proj_match<false>, dim3((unsigned)path.blocks), dim3(kThreads), 0, st, g);
-  return record_call(m, st);
+  return launch(m, path, g, k_proj_match<true>, k_proj_match<false>, stream);
 }
 
 int orbx_projmatch_search(orbx_projmatch* m, const orbx_projmatch_side* side, const orbx_projmatch_item* items, int nitems,
@@ -270,9 +258,8 @@ int orbx_projmatch_search(orbx_projmatch* m, const orbx_projmatch_side* side, co
   int rc = check(m, who, side, items, nitems, points, npts, mcap, pdesc, npoints, scale_factors, nlevels, kp_match, nmatches);
   if (rc != ORBX_OK) return rc;
   Stager io;
-  const size_t nf = (size_t)side->nframes, nk = nf * side->capacity, rows = (size_t)nitems * side->capacity;
-  const size_t o_kps = io.in(side->d_kps, nk * sizeof(orbx_keypoint)), o_desc = io.in(side->d_desc, nk * 32), o_counts = io.in(side->d_counts, nf * 8);
-  const size_t o_bounds = io.in(side->d_bounds, nf * 16);
+  const size_t rows = (size_t)nitems * side->capacity;
+  const StagedSide ss = stage_side(io, side);
   const size_t o_items = io.in(items, (size_t)nitems * sizeof(orbx_projmatch_item));
   const size_t o_pts = io.in(points, (size_t)nitems * mcap * sizeof(orbx_projmatch_point));
   const size_t o_npts = io.in(npts, (size_t)nitems * 4), o_pdesc = io.in(pdesc, (size_t)npoints * 32);
@@ -280,8 +267,7 @@ int orbx_projmatch_search(orbx_projmatch* m, const orbx_projmatch_side* side, co
   const size_t o_match = io.out(kp_match, rows * 4), o_nm = io.out(nmatches, (size_t)nitems * 4);
   if ((rc = upload(m, io)) != ORBX_OK) return rc;
   uint8_t* const d = m->io.p;
-  const orbx_projmatch_side ds = {(const orbx_keypoint*)(d + o_kps), d + o_desc, (const int32_t*)(d + o_counts), (const float*)(d + o_bounds),
-                                  side->nframes, side->capacity};
+  const orbx_projmatch_side ds = device_side(d, ss, side);
   rc = orbx_projmatch_search_device(m, &ds, (const orbx_projmatch_item*)(d + o_items), nitems, (const orbx_projmatch_point*)(d + o_pts),
                                     (const int32_t*)(d + o_npts), mcap, d + o_pdesc, npoints, scale_factors, nlevels, check_orientation,
                                     kp_taken ? d + o_taken : nullptr, (int32_t*)(d + o_match), (int32_t*)(d + o_nm), m->st);

@@ -3,23 +3,22 @@
 // and right extractions and the left/right match tables a batched rig front-end left in HBM.
 //
 // k_rig_match<LDS, LAST>: one workgroup of 8 waves per item (a grid of at most kMaxBlocks workgroups walks the items).  The frame grid, the
-// window walk and the offsets' scan are csrc/side/orbx_window_device.h's, used twice: a left and a right grid in two Arrays that share the
-// offsets, the results and the candidate room.  This file holds what is the rig's own:
+// window walk, the offsets' scan, the chunk cut, the chain's step (the scan over the open candidates, the ratio test, the bind), the last
+// writer, the rotation filter and the layout are csrc/side/orbx_window_device.h's, the grid used twice: a left and a right one in two
+// Arrays that share the offsets, the results and the candidate room.  This file holds what is the rig's own:
 //   check                the item's frame, both counts, the row's count and every in-view point's levels and pool row, the match tables'
 //                        entries (entry 1), the direction and th (entry 2), before any of them addresses memory.
 //   phase A              a LIST PER (POINT, CAMERA), list 2 q + camera: the window over that camera's grid; a candidate is one word: index
 //                        in its camera (15 bits), Hamming distance (9), octave (5, two's complement).  The distances depend on nothing in
 //                        the chain.  Chunks are cut between points, never between a point's two lists: the room holds at least
 //                        cap_l + cap_r candidates.
-//   phase B, wave 0      the chain over the chunk's points in index order: the left sub-step, then the right sub-step, each a scan of its
-//                        list by 64 lanes that passes over hidden slots (a bit per slot in LDS, right slots at cap_l + index) and one or
-//                        two DPP min-reductions.  Every write sets or clears the slot's hidden bit by the writer's obs, so the right
-//                        sub-step sees what the left one of the same point bound (entry 1's l2r binding).  The :126 and :1735 exits are
-//                        wave-uniform.  A point records up to four (entry 1) or two (entry 2) slots.
-//   phase C, all waves   kp_match[slot] = the LAST point that wrote it (an integer maximum over the writers' indices), then kp_obs[slot] =
-//                        that point's obs.
-//   phase D, all waves   entry 2 under check_orientation: the histogram over both results of every point (the left or the right keypoint's
-//                        angle by the slot), ComputeThreeMaxima, and kp_match = -2, kp_obs = -1 for every entry of another bin.
+//   phase B, wave 0      the walk over the chunk's points in index order: the left sub-step, then the right sub-step, each the core's step on
+//                        its list (a bit per slot in LDS, right slots at cap_l + index).  Every bind sets or clears the slot's hidden bit by
+//                        the writer's obs, so the right sub-step sees what the left one of the same point bound (entry 1's l2r binding).
+//                        The :126 and :1735 exits are wave-uniform.  A point records up to four (entry 1) or two (entry 2) slots.
+//   phase C, all waves   the core's last writer over those results.
+//   phase D, all waves   entry 2 under check_orientation: the core's rotation filter over both results of every point (the left or the right
+//                        keypoint's angle by the slot); kp_match = -2, kp_obs = -1 for every entry of another bin.
 // The hidden bits are 4 KiB of static LDS on both paths.
 // The float expressions are compiled with -ffp-contract=off: every operation is rounded by itself, as the specification states them.
 #include <hip/hip_runtime.h>
@@ -42,10 +41,9 @@ struct orbx_rigmatch : orbx::side::win::WindowHandle {};   // lds_limit: ORBX_RI
 namespace {
 
 using namespace orbx::side;
-using namespace orbx::side::dev;          // ld / st on the chain's state: written by one lane, read by the wave's other lanes in the next step
+using namespace orbx::side::dev;
 using namespace orbx::side::win;
 
-constexpr int kThHigh = 100;
 constexpr int kRowBytes = 48;             // both entries' point rows
 static_assert(ORBX_RIGMATCH_MAX_CAPACITY == kMaxCap && ORBX_RIGMATCH_MAX_LEVELS == kMaxLevels, "the window core's limits");
 static_assert(sizeof(orbx_rigmatch_local_point) == kRowBytes && sizeof(orbx_rigmatch_last_point) == kRowBytes, "three 16-byte loads a row");
@@ -63,27 +61,6 @@ struct Args {
   float th, ratio;
   float sf[kMaxLevels];
 };
-
-// one item's arrays, as offsets in the LDS block resp. the scratch slice (16-byte aligned): the window core's, for two grids
-struct RigLay { size_t desc_l, desc_r, keys_l, keys_r, recs_l, recs_r, cstart_l, cstart_r, offs, res, cand, fixed; };
-__host__ __device__ inline RigLay rig_layout(int cap_l, int cap_r, int mcap, int p2l, int p2r, bool lds) {
-  RigLay l;
-  size_t o = 0;
-  auto add = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 15) & ~(size_t)15; return at; };
-  l.desc_l = add(lds ? (size_t)cap_l * 32 : 0);
-  l.desc_r = add(lds ? (size_t)cap_r * 32 : 0);
-  l.keys_l = add((size_t)p2l * 4);
-  l.keys_r = add((size_t)p2r * 4);
-  l.recs_l = add((size_t)cap_l * kRecBytes);
-  l.recs_r = add((size_t)cap_r * kRecBytes);
-  l.cstart_l = add((size_t)(kCells + 1) * 2);
-  l.cstart_r = add((size_t)(kCells + 1) * 2);
-  l.offs = add((size_t)(2 * mcap + 1) * 4);   // first candidate of every (point, camera) list
-  l.res = add((size_t)mcap * 16);             // the slots a point wrote: four (entry 1) or two (entry 2) a point, -1 without
-  l.cand = o;
-  l.fixed = o;
-  return l;
-}
 
 // a (point, camera) window
 struct Pt { float x, y, radius; int lo, hi, point; bool live; };
@@ -130,66 +107,10 @@ __device__ __forceinline__ Pt load_last(const uint8_t* row, int cam, const float
   return t;
 }
 
-// the largest q1 <= nq with offs[2 q1] - offs[2 q0] <= room: a chunk ends between points; one point's two lists (<= cap_l + cap_r <= room)
-// always fit
-__device__ __forceinline__ int rig_chunk_end(const int32_t* offs, int q0, int nq, int room) {
-  const int e0 = offs[2 * q0];
-  int lo = q0 + 1, hi = nq;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (offs[2 * mid] - e0 <= room) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
-// The wave's two smallest (distance << 15 | position) keys among the list's entries whose slot (base + index) is open; all 64 lanes call
-// it.  Positions are unique, so one lane holds m1.  TWO = false: m1 alone.
-template <bool TWO>
-__device__ __forceinline__ void open_top(const uint32_t* cand, int b0, int cnt, int base, const int32_t* hidden, int lane, int& m1, int& m2) {
-  int k1 = kNone, k2 = kNone;
-  for (int j = lane; j < cnt; j += 64) {
-    const uint32_t e = cand[b0 + j];
-    const int s = base + (int)(e & 0x7FFFu);
-    if ((ld(hidden + (s >> 5)) >> (s & 31)) & 1) continue;
-    const int key = (int)((e >> 15) & 0x1FFu) << 15 | j;
-    const int hi = max(k1, key);
-    k1 = min(k1, key);
-    k2 = min(k2, hi);
-  }
-  m1 = wave_min(k1);
-  m2 = kNone;
-  if (TWO && m1 != kNone && (m1 >> 15) <= kThHigh) m2 = wave_min(k1 == m1 ? k2 : k1);
-}
-
-// :123-128 resp. :193-196 on the two keys: 0 nothing (no open candidate, or bestDist > 100), 1 the `continue` (equal octaves and
-// bestDist > mfNNratio * bestDist2), 2 the octaves differ or bestDist <= mfNNratio * bestDist2, 3 neither comparison holds (a NaN ratio)
-__device__ __forceinline__ int ratio_test(const uint32_t* cand, int b0, int m1, int m2, float ratio, int* idx) {
-  if (m1 == kNone || (m1 >> 15) > kThHigh) return 0;
-  const uint32_t e1 = cand[b0 + (m1 & 0x7FFF)];
-  const int best = m1 >> 15, level1 = (int)(e1 >> 24 & 31u);
-  int second = 256, level2 = 31;           // bestDist2 = 256, bestLevel2 = -1
-  if (m2 != kNone) {
-    second = m2 >> 15;
-    level2 = (int)(cand[b0 + (m2 & 0x7FFF)] >> 24 & 31u);
-  }
-  *idx = (int)(e1 & 0x7FFFu);
-  const float lim = ratio * (float)second;
-  if (level1 == level2 && (float)best > lim) return 1;
-  if (level1 != level2 || (float)best <= lim) return 2;
-  return 3;
-}
-
-// one lane: the slot's new holder has obs observations
-__device__ __forceinline__ void bind(int32_t* hidden, int32_t* res, int slot, int obs) {
-  st(res, slot);
-  const int w = ld(hidden + (slot >> 5)), bit = (int)(1u << (slot & 31));
-  st(hidden + (slot >> 5), obs > 0 ? w | bit : w & ~bit);
-}
-
 template <bool LDS, bool LAST>
 __global__ __launch_bounds__(kThreads) void k_rig_match(Args g) {
   extern __shared__ __align__(16) uint8_t smem[];
-  __shared__ int s_bad, s_hist[32], s_ind[3], s_removed;
+  __shared__ int s_bad;
   __shared__ int32_t s_hidden[kMaxCap / 32];   // bit s: slot s holds a map point with Observations() > 0
   __shared__ float s_sf[kMaxLevels];
   constexpr int RES = LAST ? 2 : 4;            // results a point
@@ -197,10 +118,9 @@ __global__ __launch_bounds__(kThreads) void k_rig_match(Args g) {
   const int cap_l = g.cap_l, cap_r = g.cap_r, slots = cap_l + cap_r, mcap = g.mcap;
   const RigLay L = rig_layout(cap_l, cap_r, mcap, g.p2l, g.p2r, LDS);
   uint8_t* const base = LDS ? smem : g.scratch + (size_t)blockIdx.x * g.scratch_stride;
-  int32_t *const offs = (int32_t*)(base + L.offs), *const res = (int32_t*)(base + L.res);
-  uint32_t* const cand = (uint32_t*)(base + L.cand);
-  const Arrays AL = {(uint32_t*)(base + L.keys_l), (Rec*)(base + L.recs_l), (uint16_t*)(base + L.cstart_l), offs, res, cand};
-  const Arrays AR = {(uint32_t*)(base + L.keys_r), (Rec*)(base + L.recs_r), (uint16_t*)(base + L.cstart_r), offs, res, cand};
+  const Arrays AL = arrays(base, L, L.grid_l), AR = arrays(base, L, L.grid_r);
+  int32_t *const offs = AL.offs, *const res = AL.res;
+  uint32_t* const cand = AL.cand;
   load_levels(s_sf, g.sf);
 
   for (int b = blockIdx.x; b < g.nitems; b += gridDim.x) {
@@ -264,6 +184,7 @@ __global__ __launch_bounds__(kThreads) void k_rig_match(Args g) {
       const uint8_t* const row = rows + (size_t)q * kRowBytes;
       return LAST ? load_last(row, cam, s_sf, th, direction) : load_local(row, cam, s_sf, th, g.factor);
     };
+    auto obs_of = [&](int q) { return *(const int32_t*)(rows + (size_t)q * kRowBytes + (LAST ? 24 : 32)); };
 
     // ---- phase A: both grids, the hidden bits over both slot ranges in the same trips over the keypoints
     if (LDS) {
@@ -292,7 +213,7 @@ __global__ __launch_bounds__(kThreads) void k_rig_match(Args g) {
     // ---- chunks of points whose candidates fit the room: lists with distances (all waves), then the chain (wave 0)
     int nm = 0;                            // wave 0's count of bindings
     for (int q0 = 0; q0 < nq;) {
-      const int e0 = offs[2 * q0], q1 = rig_chunk_end(offs, q0, nq, g.room);
+      const int e0 = offs[2 * q0], q1 = chunk_end<2>(offs, q0, nq, g.room);
       const int tot = min(offs[2 * q1] - e0, g.room);
       for (int p = 2 * q0 + tid; p < 2 * q1; p += kThreads) {
         int k = offs[p] - e0;
@@ -321,7 +242,7 @@ __global__ __launch_bounds__(kThreads) void k_rig_match(Args g) {
           if (lane < cn) {
             const int q = c0 + lane;
             l_bl = offs[2 * q] - e0; l_br = offs[2 * q + 1] - e0; l_nl = l_br - l_bl; l_nr = offs[2 * q + 2] - e0 - l_br;
-            l_obs = *(const int32_t*)(rows + (size_t)q * kRowBytes + (LAST ? 24 : 32));
+            l_obs = obs_of(q);
           }
           for (int i = 0; i < cn; i++) {
             const int cnt_l = __builtin_amdgcn_readlane(l_nl, i), cnt_r = __builtin_amdgcn_readlane(l_nr, i);
@@ -329,47 +250,50 @@ __global__ __launch_bounds__(kThreads) void k_rig_match(Args g) {
             const int bl = __builtin_amdgcn_readlane(l_bl, i), br = __builtin_amdgcn_readlane(l_br, i);
             const int obs = __builtin_amdgcn_readlane(l_obs, i);
             int32_t* const out = res + (size_t)(c0 + i) * RES;
-            int m1, m2, idx = 0;
+            LaneKeys mine;
+            int m1, idx = 0;
             if (LAST) {
-              open_top<false>(cand, bl, cnt_l, 0, s_hidden, lane, m1, m2);
+              m1 = open_top(cand, bl, cnt_l, 0, s_hidden, lane);
               if (m1 != kNone && (m1 >> 15) <= kThHigh) {        // :1770
-                if (lane == 0) bind(s_hidden, out, (int)(cand[bl + (m1 & 0x7FFF)] & 0x7FFFu), obs);
+                if (lane == 0) bind<true>(s_hidden, out, (int)(cand[bl + (m1 & 0x7FFF)] & 0x7FFFu), obs);
                 nm++;
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // the stores are done before the next loads
+                publish();
               }
               if (cnt_r <= 0) continue;
-              open_top<false>(cand, br, cnt_r, cap_l, s_hidden, lane, m1, m2);
+              m1 = open_top(cand, br, cnt_r, cap_l, s_hidden, lane);
               if (m1 != kNone && (m1 >> 15) <= kThHigh) {        // :1836
-                if (lane == 0) bind(s_hidden, out + 1, cap_l + (int)(cand[br + (m1 & 0x7FFF)] & 0x7FFFu), obs);
+                if (lane == 0) bind<true>(s_hidden, out + 1, cap_l + (int)(cand[br + (m1 & 0x7FFF)] & 0x7FFFu), obs);
                 nm++;
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+                publish();
               }
             } else {
               if (cnt_l > 0) {
-                open_top<true>(cand, bl, cnt_l, 0, s_hidden, lane, m1, m2);
+                m1 = open_top(cand, bl, cnt_l, 0, s_hidden, lane, &mine);
+                const int m2 = (m1 >> 15) <= kThHigh ? open_second(mine, m1) : kNone;
                 const int rc = ratio_test(cand, bl, m1, m2, g.ratio, &idx);
                 if (rc == 1) continue;     // :126: the point is done, its right block too
                 if (rc == 2) {
                   const int x = g.l2r[ofl + idx];   // idx < nl; the entry lies in [-1, nr): the check
                   if (lane == 0) {
-                    bind(s_hidden, out, idx, obs);
-                    if (x >= 0) bind(s_hidden, out + 1, cap_l + x, obs);   // :131-135, whatever the slot held
+                    bind<true>(s_hidden, out, idx, obs);
+                    if (x >= 0) bind<true>(s_hidden, out + 1, cap_l + x, obs);   // :131-135, whatever the slot held
                   }
                   nm += 1 + (x >= 0);
-                  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // the right block sees these
+                  publish();               // the right block sees these
                 }
               }
               if (cnt_r <= 0) continue;
-              open_top<true>(cand, br, cnt_r, cap_l, s_hidden, lane, m1, m2);
+              m1 = open_top(cand, br, cnt_r, cap_l, s_hidden, lane, &mine);
+              const int m2 = (m1 >> 15) <= kThHigh ? open_second(mine, m1) : kNone;
               const int rc = ratio_test(cand, br, m1, m2, g.ratio, &idx);
               if (rc >= 2) {               // :193-208: everything but the `continue`
                 const int x = g.r2l[ofr + idx];
                 if (lane == 0) {
-                  if (x >= 0) bind(s_hidden, out + 2, x, obs);             // :198-202
-                  bind(s_hidden, out + 3, cap_l + idx, obs);
+                  if (x >= 0) bind<true>(s_hidden, out + 2, x, obs);             // :198-202
+                  bind<true>(s_hidden, out + 3, cap_l + idx, obs);
                 }
                 nm += 1 + (x >= 0);
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+                publish();
               }
             }
           }
@@ -380,56 +304,14 @@ __global__ __launch_bounds__(kThreads) void k_rig_match(Args g) {
       q0 = q1;
     }
 
-    // ---- phase C: the last point that wrote a slot holds it; integer maxima, so the order does not matter
-    for (int e = tid; e < RES * nq; e += kThreads) {
-      const int s = res[e];
-      if (s >= 0 && s < slots) __hip_atomic_fetch_max(omatch + s, e / RES, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    for (int s = tid; s < slots; s += kThreads) {
-      const int q = __hip_atomic_load(omatch + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (q >= 0 && q < nq) oobs[s] = *(const int32_t*)(rows + (size_t)q * kRowBytes + (LAST ? 24 : 32));
-    }
+    last_writer<kThreads, RES>(res, nq, slots, omatch, oobs, obs_of);   // ---- phase C
     int removed = 0;
-    if (LAST && g.check_ori) {             // uniform over the grid
-      // ---- phase D: the rotation histogram (:1775-1792, :1840-1856), its three maxima and the removal (:1864-1884)
-      if (tid < 32) s_hist[tid] = 0;
-      if (tid == 0) s_removed = 0;
-      __syncthreads();                     // and phase C's reads of kp_match and writes of kp_obs are done
-      for (int e = tid; e < RES * nq; e += kThreads) {
-        const int s = res[e];
-        if (s < 0 || s >= slots) continue;
-        const float a = s < cap_l ? kp_field<float>(kpl, s, kAngle) : kp_field<float>(kpr, s - cap_l, kAngle);   // a written slot is below its count
-        const int bin = rot_bin(*(const float*)(rows + (size_t)(e / RES) * kRowBytes + 16), a);
-        if (bin >= 0) atomicAdd(&s_hist[bin], 1);
-        res[e] = s | (bin + 1) << 16;      // s < 32768; bin + 1 in 0 .. 30
-      }
-      __syncthreads();
-      if (tid == 0) {                      // ComputeThreeMaxima (:2012-2053)
-        int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
-        for (int i = 0; i < kBins; i++) {
-          const int s = s_hist[i];
-          if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-          else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-          else if (s > max3) { max3 = s; ind3 = i; }
-        }
-        if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-        else if ((float)max3 < 0.1f * (float)max1) { ind3 = -1; }
-        s_ind[0] = ind1; s_ind[1] = ind2; s_ind[2] = ind3;
-      }
-      __syncthreads();
-      const int ind1 = s_ind[0], ind2 = s_ind[1], ind3 = s_ind[2];
-      for (int e = tid; e < RES * nq; e += kThreads) {
-        const int r = res[e];
-        if (r < 0) continue;
-        const int bin = (r >> 16) - 1, s = r & 0xFFFF;
-        if (bin < 0 || bin == ind1 || bin == ind2 || bin == ind3) continue;
-        omatch[s] = -2; oobs[s] = -1;      // entries of one slot write the same values
-        atomicAdd(&s_removed, 1);
-      }
-      __syncthreads();
-      removed = s_removed;
-    }
+    // ---- phase D: the rotation histogram (:1775-1792, :1840-1856), its three maxima and the removal (:1864-1884)
+    if (LAST && g.check_ori)               // uniform over the grid; its first barrier: phase C's reads of kp_match and writes of kp_obs are done
+      removed = rotation_filter<kThreads, RES>(
+          res, nq, slots, [&](int q) { return *(const float*)(rows + (size_t)q * kRowBytes + 16); },
+          [&](int s) { return s < cap_l ? kp_field<float>(kpl, s, kAngle) : kp_field<float>(kpr, s - cap_l, kAngle); },   // a written slot is below its count
+          [&](int s) { omatch[s] = -2; oobs[s] = -1; });   // entries of one slot write the same values
     if (tid == 0) g.nmatches[b] = nm - removed;
   }
 }
@@ -460,12 +342,9 @@ int launch(orbx_rigmatch* m, const char* who, const orbx_rigmatch_side* side, co
   if (rc != ORBX_OK) return rc;
   ORBX_SIDE_HIP(m, hipSetDevice(m->device));
   const int cap_l = side->cap_l, cap_r = side->cap_r;
-  int p2l = 2, p2r = 2;
-  while (p2l < cap_l) p2l <<= 1;
-  while (p2r < cap_r) p2r <<= 1;
+  const int p2l = sort_size(cap_l), p2r = sort_size(cap_r);
   Paths path;                              // one point's longest pair of lists is cap_l + cap_r candidates
-  rc = plan_paths(m, m->lds_limit, rig_layout(cap_l, cap_r, mcap, p2l, p2r, true).fixed, rig_layout(cap_l, cap_r, mcap, p2l, p2r, false).fixed,
-                  cap_l + cap_r, nitems, {kMaxBlocks, kGlobalBlocks, kGlobalRoom}, &path);
+  rc = plan(m, rig_layout(cap_l, cap_r, mcap, p2l, p2r, true).fixed, rig_layout(cap_l, cap_r, mcap, p2l, p2r, false).fixed, cap_l + cap_r, nitems, &path);
   if (rc != ORBX_OK) return rc;
   Args g;
   g.kps_l = (const uint8_t*)side->d_kps_l; g.desc_l = side->d_desc_l; g.counts_l = side->d_counts_l;
@@ -474,32 +353,27 @@ int launch(orbx_rigmatch* m, const char* who, const orbx_rigmatch_side* side, co
   g.frames = LAST ? nullptr : (const int32_t*)d_items; g.items = LAST ? (const orbx_rigmatch_last_item*)d_items : nullptr;
   g.rows = (const uint8_t*)d_rows; g.nrows = d_nrows; g.pdesc = d_pdesc;
   g.kp_obs = d_kp_obs; g.kp_match = d_kp_match; g.nmatches = d_nmatches;
-  g.scratch = path.in_lds ? nullptr : m->scratch.p; g.scratch_stride = path.scratch_stride;
   g.nframes = side->nframes; g.cap_l = cap_l; g.cap_r = cap_r; g.nitems = nitems; g.mcap = mcap; g.npoints = npoints; g.nlevels = nlevels;
-  g.p2l = p2l; g.p2r = p2r; g.room = path.room;
+  g.p2l = p2l; g.p2r = p2r;
   g.factor = (double)th != 1.0;            // bFactor, src/ORBmatcher.cc:47
   g.check_ori = check_orientation != 0;
   g.th = th; g.ratio = nn_ratio;
   fill_levels(g.sf, scale_factors, nlevels);
-  hipStream_t st = stream ? (hipStream_t)stream : m->st;
-  if ((rc = wait_previous(m, st)) != ORBX_OK) return rc;
-  if (path.in_lds) hipLaunchKernelGGL((k_rig_match<true, LAST>), dim3((unsigned)path.blocks), dim3(kThreads), path.lds_bytes, st, g);
-  else hipLaunchKernelGGL((k_rig_match<false, LAST>), dim3((unsigned)path.blocks), dim3(kThreads), 0, st, g);
-  return record_call(m, st);
+  return win::launch(m, path, g, k_rig_match<true, LAST>, k_rig_match<false, LAST>, stream);
 }
 
-// a host form's side in the handle's io block
-struct StagedSide { size_t kl, dl, cl, kr, dr, cr, l2r, r2l, bounds; };
-StagedSide stage_side(Stager& io, const orbx_rigmatch_side* s, bool tables) {
+// a host form's side in the handle's io block: two cameras and the tables
+struct RigStaged { size_t kl, dl, cl, kr, dr, cr, l2r, r2l, bounds; };
+RigStaged stage_side(Stager& io, const orbx_rigmatch_side* s, bool tables) {
   const size_t nf = (size_t)s->nframes, nkl = nf * s->cap_l, nkr = nf * s->cap_r;
-  StagedSide o;
+  RigStaged o;
   o.kl = io.in(s->d_kps_l, nkl * sizeof(orbx_keypoint)); o.dl = io.in(s->d_desc_l, nkl * 32); o.cl = io.in(s->d_counts_l, nf * 8);
   o.kr = io.in(s->d_kps_r, nkr * sizeof(orbx_keypoint)); o.dr = io.in(s->d_desc_r, nkr * 32); o.cr = io.in(s->d_counts_r, nf * 8);
   o.l2r = tables ? io.in(s->d_l2r, nkl * 4) : 0; o.r2l = tables ? io.in(s->d_r2l, nkr * 4) : 0;
   o.bounds = io.in(s->d_bounds, nf * 16);
   return o;
 }
-orbx_rigmatch_side device_side(uint8_t* d, const StagedSide& o, const orbx_rigmatch_side* s, bool tables) {
+orbx_rigmatch_side device_side(uint8_t* d, const RigStaged& o, const orbx_rigmatch_side* s, bool tables) {
   return {(const orbx_keypoint*)(d + o.kl), d + o.dl, (const int32_t*)(d + o.cl), (const orbx_keypoint*)(d + o.kr), d + o.dr,
           (const int32_t*)(d + o.cr), tables ? (const int32_t*)(d + o.l2r) : nullptr, tables ? (const int32_t*)(d + o.r2l) : nullptr,
           (const float*)(d + o.bounds), s->nframes, s->cap_l, s->cap_r};
@@ -543,7 +417,7 @@ int orbx_rigmatch_local(orbx_rigmatch* m, const orbx_rigmatch_side* side, const 
   if (rc != ORBX_OK) return rc;
   Stager io;
   const size_t rows = (size_t)nitems * (side->cap_l + side->cap_r);
-  const StagedSide ss = stage_side(io, side, true);
+  const RigStaged ss = stage_side(io, side, true);
   const size_t o_frames = io.in(frames, (size_t)nitems * 4), o_mp = io.in(mp, (size_t)nitems * mcap * kRowBytes);
   const size_t o_nmp = io.in(nmp, (size_t)nitems * 4), o_pdesc = io.in(pdesc, (size_t)npoints * 32);
   const size_t o_obs = io.out(kp_obs, rows * 4, true), o_match = io.out(kp_match, rows * 4), o_nm = io.out(nmatches, (size_t)nitems * 4);
@@ -580,7 +454,7 @@ int orbx_rigmatch_last(orbx_rigmatch* m, const orbx_rigmatch_side* side, const o
   if (rc != ORBX_OK) return rc;
   Stager io;
   const size_t rows = (size_t)nitems * (side->cap_l + side->cap_r);
-  const StagedSide ss = stage_side(io, side, false);
+  const RigStaged ss = stage_side(io, side, false);
   const size_t o_items = io.in(items, (size_t)nitems * sizeof(orbx_rigmatch_last_item)), o_pts = io.in(points, (size_t)nitems * mcap * kRowBytes);
   const size_t o_nlast = io.in(nlast, (size_t)nitems * 4), o_pdesc = io.in(pdesc, (size_t)npoints * 32);
   const size_t o_obs = io.out(kp_obs, rows * 4, true), o_match = io.out(kp_match, rows * 4), o_nm = io.out(nmatches, (size_t)nitems * 4);

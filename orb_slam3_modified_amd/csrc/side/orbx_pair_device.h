@@ -1,7 +1,7 @@
 // The device helpers the side libraries' matching kernels share: descriptors and Hamming distances, the wave minimum, the 32-bit top-2
 // keys, a chain's relaxed loads and stores, the rotation bin, the keypoint field reader, the LDS-DMA staging, a frame grid's record, a work
 // list's pop and the workgroup scan.  Every source below csrc/ that includes this file is a user; the frame grid and the window of the
-// three chained projection matchers are built on it in orbx_window_device.h.  Device code only; it sits below csrc/, outside
+// four chained projection matchers are built on it in orbx_window_device.h.  Device code only; it sits below csrc/, outside
 // kernels_hash().  A kernel's file imports the names with `using namespace orbx::side::dev;` inside its anonymous namespace.
 // ComputeThreeMaxima and the trip loop's three-reduction merge stay written out in k_match_pairs and k_init_pairs: as functions of this
 // header they change those kernels' instruction streams (the compiler unrolls and schedules them differently).

@@ -1,14 +1,21 @@
-// The frame-grid window core of the three chained projection matchers (liborbx_localmatch.so, liborbx_lastmatch.so, liborbx_projmatch.so):
-// what k_local_match, k_last_match and k_proj_match share, stated once.  Their shape is one 512-thread workgroup per item:
+// The frame-grid window core of the four chained projection matchers (liborbx_localmatch.so, liborbx_lastmatch.so, liborbx_projmatch.so,
+// liborbx_rigmatch.so): what k_local_match, k_last_match, k_proj_match and k_rig_match share, stated once.  Their shape is one 512-thread
+// workgroup per item (the rig: two grids, a list per (point, camera), RES = 4 or 2 results a point):
 //   check                the item's indices and counts, before any of them addresses memory (each kernel's own)
 //   phase A, all waves   build_grid: the frame's keypoints as keys (cell << 16 | index), sorted (bitonic; the keys are unique, so the order is
 //                        the frame grid's: cells x-major, then y, then ascending index), a 16-byte record per sorted position, the cells'
 //                        starts by binary search.  A LANE PER POINT walks its window (walk) twice: once to count and, after scan_offsets,
 //                        for a chunk of points whose lists fit the candidate room (chunk_end), once to write its list.
-//   phase B, wave 0      the chain over the chunk's points in index order (each kernel's own)
-//   phase D, all waves   rotation_filter: the accepted points' bins, ComputeThreeMaxima, the removal (last-frame and projection matchers)
-// LDS path: the frame's descriptors, the grid, the offsets, the points' results and the candidate room in LDS (layout); global path: the
-// descriptors where they lie, everything else in the workgroup's slice of the handle's scratch.
+//   phase B, wave 0      the chain over the chunk's points in index order.  A step is open_top (64 lanes pass over the list's entries
+//                        whose slot's bit is set and keep their smallest one or two (distance << 15 | position) keys, then a DPP
+//                        min-reduction; open_second, behind the caller's gate, is the second), the kernel's accept test (ratio_test on two keys), bind by one lane (the slot into the point's
+//                        results, the slot's bit) and publish.  The walk over a chunk's points (a lane preloads a point's list bounds and
+//                        obs, readlane hands them out) and what a step writes beyond the bit are each kernel's own.
+//   phase C, all waves   last_writer: kp_match[slot] = the LAST point that wrote it, kp_obs[slot] = that point's obs (not k_proj_match:
+//                        there a slot is bound once, by the chain itself)
+//   phase D, all waves   rotation_filter: the results' bins, ComputeThreeMaxima, the removal (not k_local_match)
+// LDS path: the frame's descriptors, the grid, the offsets, the points' results and the candidate room in LDS (layout, rig_layout); global
+// path: the descriptors where they lie, everything else in the workgroup's slice of the handle's scratch.
 // The part above __HIPCC__ is plain C++ (tests/support/window_check.cpp compiles it with the host compiler); the rest is device code,
 // included after orbx_pair_device.h.  It sits below csrc/, outside kernels_hash().
 #pragma once
@@ -37,6 +44,7 @@ constexpr int kMaxLevels = 16;
 constexpr int kCols = 64, kRows = 48, kCells = kCols * kRows;
 constexpr int kBins = 30;
 constexpr int kNone = INT_MAX;            // no key
+constexpr int kThHigh = 100;              // ORBmatcher::TH_HIGH
 constexpr int kRecBytes = 16;             // sizeof(dev::Rec)
 static_assert(kMaxCap == 1 << 15, "15-bit indices and positions");
 
@@ -72,20 +80,43 @@ ORBX_WINDOW_HD inline float div_rn(float a, float b) {
   return r;
 }
 
-// one item's arrays, as offsets in the LDS block resp. the scratch slice (16-byte aligned)
-struct Lay { size_t desc, keys, recs, cstart, offs, res, cand, fixed; };
+// One item's arrays, as offsets in the LDS block resp. the scratch slice (16-byte aligned).  A grid's block: the sorted
+// (cell << 16 | index) keys of a frame's keypoints, their records in the same order, the first sorted position of every cell.
+struct Bump {
+  size_t o = 0;
+  ORBX_WINDOW_HD size_t add(size_t bytes) { const size_t at = o; o = (o + bytes + 15) & ~(size_t)15; return at; }
+};
+struct GridLay { size_t keys, recs, cstart; };
+ORBX_WINDOW_HD inline GridLay grid_layout(Bump& b, int cap, int p2) {
+  GridLay g;
+  g.keys = b.add((size_t)p2 * 4);
+  g.recs = b.add((size_t)cap * kRecBytes);
+  g.cstart = b.add((size_t)(kCells + 1) * 2);
+  return g;
+}
+struct Lay { size_t desc; GridLay grid; size_t offs, res, cand, fixed; };
 ORBX_WINDOW_HD inline Lay layout(int cap, int mcap, int p2, bool lds) {
   Lay l;
-  size_t o = 0;
-  auto add = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 15) & ~(size_t)15; return at; };
-  l.desc = add(lds ? (size_t)cap * 32 : 0);
-  l.keys = add((size_t)p2 * 4);             // sorted (cell << 16 | index) of the frame's keypoints
-  l.recs = add((size_t)cap * kRecBytes);    // their records, in the same order
-  l.cstart = add((size_t)(kCells + 1) * 2); // first sorted position of every cell
-  l.offs = add((size_t)(mcap + 1) * 4);     // first candidate of every point (exclusive scan of the counts)
-  l.res = add((size_t)mcap * 4);            // the keypoint a point was accepted with (rotation_filter: its bin + 1 above bit 16), -1 without
-  l.cand = o;
-  l.fixed = o;
+  Bump b;
+  l.desc = b.add(lds ? (size_t)cap * 32 : 0);
+  l.grid = grid_layout(b, cap, p2);
+  l.offs = b.add((size_t)(mcap + 1) * 4);   // first candidate of every point (exclusive scan of the counts)
+  l.res = b.add((size_t)mcap * 4);          // the keypoint a point was accepted with (rotation_filter: its bin + 1 above bit 16), -1 without
+  l.cand = l.fixed = b.o;
+  return l;
+}
+// the rig's: two grids
+struct RigLay { size_t desc_l, desc_r; GridLay grid_l, grid_r; size_t offs, res, cand, fixed; };
+ORBX_WINDOW_HD inline RigLay rig_layout(int cap_l, int cap_r, int mcap, int p2l, int p2r, bool lds) {
+  RigLay l;
+  Bump b;
+  l.desc_l = b.add(lds ? (size_t)cap_l * 32 : 0);
+  l.desc_r = b.add(lds ? (size_t)cap_r * 32 : 0);
+  l.grid_l = grid_layout(b, cap_l, p2l);
+  l.grid_r = grid_layout(b, cap_r, p2r);
+  l.offs = b.add((size_t)(2 * mcap + 1) * 4);   // first candidate of every (point, camera) list
+  l.res = b.add((size_t)mcap * 16);             // the slots a point wrote: four (entry 1) or two (entry 2) a point, -1 without
+  l.cand = l.fixed = b.o;
   return l;
 }
 
@@ -97,9 +128,10 @@ constexpr size_t kX = offsetof(orbx_keypoint, x), kY = offsetof(orbx_keypoint, y
                  kAngle = offsetof(orbx_keypoint, angle);
 
 struct Arrays { uint32_t* keys; Rec* recs; uint16_t* cstart; int32_t* offs; int32_t* res; uint32_t* cand; };
-__device__ __forceinline__ Arrays arrays(uint8_t* base, const Lay& L) {
-  return {(uint32_t*)(base + L.keys), (Rec*)(base + L.recs), (uint16_t*)(base + L.cstart), (int32_t*)(base + L.offs), (int32_t*)(base + L.res),
-          (uint32_t*)(base + L.cand)};
+template <class L>                        // Lay or RigLay: a grid of the layout with the layout's offsets, results and candidate room
+__device__ __forceinline__ Arrays arrays(uint8_t* base, const L& lay, const GridLay& g) {
+  return {(uint32_t*)(base + g.keys), (Rec*)(base + g.recs), (uint16_t*)(base + g.cstart), (int32_t*)(base + lay.offs), (int32_t*)(base + lay.res),
+          (uint32_t*)(base + lay.cand)};
 }
 
 // the level table into LDS: constant indices into the kernel's arguments
@@ -219,33 +251,108 @@ __device__ __forceinline__ void scan_offsets(int32_t* offs, int m) {
   for (int i = lo; i < hi; i++) { const int c = offs[i]; offs[i] = run; run += c; }
 }
 
-// the chunk of points from q0: the largest q1 <= nq with offs[q1] - offs[q0] <= room; one point's list (<= cap <= room) always fits
+// the chunk of points from q0, LISTS lists a point: the largest q1 <= nq with offs[LISTS q1] - offs[LISTS q0] <= room.  A chunk ends
+// between points; one point's lists (<= the slots <= room) always fit
+template <int LISTS = 1>
 __device__ __forceinline__ int chunk_end(const int32_t* offs, int q0, int nq, int room) {
-  const int e0 = offs[q0];
+  const int e0 = offs[LISTS * q0];
   int lo = q0 + 1, hi = nq;
   while (lo < hi) {
     const int mid = (lo + hi + 1) >> 1;
-    if (offs[mid] - e0 <= room) lo = mid; else hi = mid - 1;
+    if (offs[LISTS * mid] - e0 <= room) lo = mid; else hi = mid - 1;
   }
   return lo;
 }
 
-// Phase D, all waves: the rotation histogram of the accepted points (res[q] = keypoint below n; angle(q) the point's angle) by integer adds
-// into 30 LDS counters, ComputeThreeMaxima (src/ORBmatcher.cc:2012-2053) by one lane, then remove(keypoint) for every entry of another bin.
-// Returns the number of entries removed.  Begins with a barrier and ends with one.
-template <int THREADS, class A, class R>
-__device__ __forceinline__ int rotation_filter(int32_t* res, int nq, int n, const uint8_t* kp, A angle, R remove) {
+// ---- phase B, wave 0.  The chain's state (the bits, the points' results) is written by one lane and read by the wave's other lanes in
+// the next step: ld / st, and publish between a step's binds and the next step's loads.
+// The wave's smallest (distance << 15 | position) key among the list's entries cand[b0 .. b0 + cnt) whose slot (base + index) is open: its
+// bit in `bits` is clear; kNone without one (kNone >> 15 is above every distance).  All 64 lanes call it.  `mine`, for a two-key caller:
+// the lane's own two smallest keys, from which open_second forms the wave's second smallest once the caller's gate on the first has
+// passed: the caller's branch stands between the two reductions.
+struct LaneKeys { int k1, k2; };
+__device__ __forceinline__ int open_top(const uint32_t* cand, int b0, int cnt, int base, const int32_t* bits, int lane, LaneKeys* mine = nullptr) {
+  int k1 = kNone, k2 = kNone;
+  for (int j = lane; j < cnt; j += 64) {
+    const uint32_t e = cand[b0 + j];
+    const int s = base + (int)(e & 0x7FFFu);
+    if ((ld(bits + (s >> 5)) >> (s & 31)) & 1) continue;
+    const int key = (int)((e >> 15) & 0x1FFu) << 15 | j;
+    const int hi = max(k1, key);
+    k1 = min(k1, key);
+    k2 = min(k2, hi);
+  }
+  if (mine) *mine = {k1, k2};
+  return wave_min(k1);
+}
+// positions are unique, so one lane holds m1: its second key stands in, every other lane's first
+__device__ __forceinline__ int open_second(const LaneKeys& mine, int m1) { return wave_min(mine.k1 == m1 ? mine.k2 : mine.k1); }
+
+// src/ORBmatcher.cc:117-130 resp. :193-196 on the two keys, whose entries carry the octaves above bit 24: 0 nothing (no open candidate, or
+// bestDist > kThHigh), 1 the `continue` (equal octaves and bestDist > mfNNratio * bestDist2), 2 the octaves differ or bestDist <=
+// mfNNratio * bestDist2, 3 neither comparison holds (a NaN ratio).  *idx: the best entry's index, for every outcome but 0.
+__device__ __forceinline__ int ratio_test(const uint32_t* cand, int b0, int m1, int m2, float ratio, int* idx) {
+  if ((m1 >> 15) > kThHigh) return 0;      // kNone too
+  const uint32_t e1 = cand[b0 + (m1 & 0x7FFF)];
+  const int best = m1 >> 15, level1 = (int)(e1 >> 24 & 31u);
+  int second = 256, level2 = 31;           // bestDist2 = 256, bestLevel2 = -1
+  if (m2 != kNone) {
+    second = m2 >> 15;
+    level2 = (int)(cand[b0 + (m2 & 0x7FFF)] >> 24 & 31u);
+  }
+  *idx = (int)(e1 & 0x7FFFu);
+  if (level1 != level2) return 2;          // first: most steps end here, before the float compare
+  const float lim = ratio * (float)second;
+  return (float)best > lim ? 1 : (float)best <= lim ? 2 : 3;
+}
+
+// One lane: the point's result *res = slot, and the slot's bit set (its new holder has obs > 0 observations) or cleared.  CLEAR = false:
+// the slot was open, as in the one-camera matchers, so clearing is a no-op and the bit's word is touched for obs > 0 alone (the
+// unconditional load and store cost k_local_match and k_last_match 3 to 4 % of a call: profiles/chain_core_refactor.txt).
+template <bool CLEAR>
+__device__ __forceinline__ void bind(int32_t* bits, int32_t* res, int slot, int obs) {
+  st(res, slot);
+  if (!CLEAR && obs <= 0) return;
+  const int w = ld(bits + (slot >> 5)), bit = (int)(1u << (slot & 31));
+  st(bits + (slot >> 5), obs > 0 ? w | bit : w & ~bit);
+}
+// all lanes, after a step's binds: the stores are done before the next step's loads
+__device__ __forceinline__ void publish() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); }
+
+// Phase C, all waves: match[slot] = the LAST of the nq points that wrote the slot (res: RES results a point, a slot below `slots` or -1;
+// an integer maximum over the writers' indices, so the order does not matter), then obs[slot] = obs_of(that point).  A barrier lies
+// between the two; the caller's follows.
+template <int THREADS, int RES, class O>
+__device__ __forceinline__ void last_writer(const int32_t* res, int nq, int slots, int32_t* match, int32_t* obs, O obs_of) {
+  const int tid = threadIdx.x;
+  for (int e = tid; e < RES * nq; e += THREADS) {
+    const int s = res[e];
+    if (s >= 0 && s < slots) __hip_atomic_fetch_max(match + s, e / RES, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __syncthreads();
+  for (int s = tid; s < slots; s += THREADS) {
+    const int q = __hip_atomic_load(match + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (q >= 0 && q < nq) obs[s] = obs_of(q);
+  }
+}
+
+// Phase D, all waves: the rotation histogram of the nq points' results (res: RES results a point, a slot below `slots` or -1; angle(q) the
+// point's angle, angle_of(slot) the slot's keypoint's) by integer adds into 30 LDS counters, ComputeThreeMaxima
+// (src/ORBmatcher.cc:2012-2053) by one lane, then remove(slot) for every entry of another bin.  Returns the number of entries removed.
+// Begins with a barrier and ends with one.
+template <int THREADS, int RES, class A, class K, class R>
+__device__ __forceinline__ int rotation_filter(int32_t* res, int nq, int slots, A angle, K angle_of, R remove) {
   __shared__ int s_hist[32], s_ind[3], s_removed;
   const int tid = threadIdx.x;
   if (tid < 32) s_hist[tid] = 0;
   if (tid == 0) s_removed = 0;
   __syncthreads();
-  for (int q = tid; q < nq; q += THREADS) {
-    const int i = res[q];
-    if (i < 0 || i >= n) continue;
-    const int bin = rot_bin(angle(q), kp_field<float>(kp, i, kAngle));
+  for (int e = tid; e < RES * nq; e += THREADS) {
+    const int i = res[e];
+    if (i < 0 || i >= slots) continue;
+    const int bin = rot_bin(angle(e / RES), angle_of(i));
     if (bin >= 0) atomicAdd(&s_hist[bin], 1);
-    res[q] = i | (bin + 1) << 16;          // i < 32768; bin + 1 in 0 .. 30
+    res[e] = i | (bin + 1) << 16;          // i < 32768; bin + 1 in 0 .. 30
   }
   __syncthreads();
   if (tid == 0) {
@@ -262,10 +369,10 @@ __device__ __forceinline__ int rotation_filter(int32_t* res, int nq, int n, cons
   }
   __syncthreads();
   const int ind1 = s_ind[0], ind2 = s_ind[1], ind3 = s_ind[2];
-  for (int q = tid; q < nq; q += THREADS) {
-    const int r = res[q];
+  for (int e = tid; e < RES * nq; e += THREADS) {
+    const int r = res[e];
     if (r < 0) continue;
-    const int bin = (r >> 16) - 1, i = r & 0xFFFF;   // i < n: only such results were given a bin
+    const int bin = (r >> 16) - 1, i = r & 0xFFFF;   // i < slots: only such results were given a bin
     if (bin < 0 || bin == ind1 || bin == ind2 || bin == ind3) continue;
     remove(i);
     atomicAdd(&s_removed, 1);

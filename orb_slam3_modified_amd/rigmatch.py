@@ -12,7 +12,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._window import LDS_MAX, MAX_CAPACITY, MAX_LEVELS, _table, _up16  # noqa: F401  (re-exported)
+from ._window import LDS_MAX, MAX_CAPACITY, MAX_LEVELS, _table, rig_lds_bytes as lds_bytes  # noqa: F401  (re-exported)
 from ._lib import KP_DTYPE, OrbxRigMatchSide, addr, host_array as arr, host_view, ptr
 
 LOCAL_POINT_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("view_cos", "<f4"), ("level", "<i4"), ("proj_xr", "<f4"), ("proj_yr", "<f4"),
@@ -21,21 +21,6 @@ LAST_ITEM_DTYPE = np.dtype([("frame", "<i4"), ("direction", "<i4"), ("th", "<f4"
 LAST_POINT_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("u_r", "<f4"), ("v_r", "<f4"), ("angle", "<f4"), ("octave", "<i4"), ("obs", "<i4"),
                              ("point", "<i4"), ("valid", "<i4"), ("reserved", "<i4", (3,))])
 assert LOCAL_POINT_DTYPE.itemsize == 48 and LAST_POINT_DTYPE.itemsize == 48 and LAST_ITEM_DTYPE.itemsize == 16
-
-
-def lds_bytes(cap_l: int, cap_r: int, mcap: int) -> int:
-    """rig_layout(cap_l, cap_r, mcap, ..., true).fixed: what the LDS path needs beside the candidate room: both descriptor sets, both grids
-    (sorted keys, records, cell starts), the offsets of 2 mcap lists and four results a point.  A call takes the LDS path when this plus
-    cap_l + cap_r candidates (one point's longest pair of lists) is within the handle's limit; the rest of the limit is candidate room
-    (4 bytes a candidate)."""
-    p2 = []
-    for cap in (cap_l, cap_r):
-        p = 2
-        while p < cap:
-            p <<= 1
-        p2.append(p)
-    cells = 2 * (64 * 48 + 1)
-    return sum(_up16(b) for b in (32 * cap_l, 32 * cap_r, 4 * p2[0], 4 * p2[1], 16 * cap_l, 16 * cap_r, cells, cells, 4 * (2 * mcap + 1), 16 * mcap))
 
 
 @dataclass

@@ -1,12 +1,12 @@
 // The plain-C++ part of csrc/side/orbx_window_device.h on the host (tests/test_window_core.py): div_rn against the IEEE float division it
-// restates, bit for bit, and layout()'s sizes for the binding's lds_bytes.
+// restates, bit for bit, and layout()'s and rig_layout()'s sizes for the bindings' lds_bytes.
 //   div     a in {64, 48} over planted b (zeros, subnormals, FLT_MIN, the floats around the overflow of a / b near 1.9e-37, FLT_MAX,
 //           infinities, a quiet NaN), over EVERY significand of b in two binades and both signs (2^25 divisors per a: whatever rounding case
 //           a division by a normal b can meet is among them), and over 4 million random normal b.
 //           An exact tie and the carry m == 0x1000000 cannot occur in a float division: a tie needs a quotient of 25 significant bits whose
 //           product with b has at most 24, and a quotient below 2 is at most 2 - 2^-23, which is representable.  The sweep holds the
 //           quotients nearest to both.
-//   layout  `layout <cap> <mcap> <fixed>` lines for the LDS path and `lds_max <kLdsMax>`.
+//   layout  `layout <cap> <mcap> <fixed>` and `rig_layout <cap_l> <cap_r> <mcap> <fixed>` lines for the LDS path and `lds_max <kLdsMax>`.
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
@@ -67,6 +67,13 @@ int main() {
     int p2 = 2;
     while (p2 < s[0]) p2 <<= 1;
     printf("layout %d %d %zu\n", s[0], s[1], orbx::side::win::layout(s[0], s[1], p2, true).fixed);
+  }
+  const int rig_shapes[5][3] = {{1, 1, 1}, {96, 80, 128}, {1024, 1024, 2048}, {1500, 1500, 2000}, {16384, 16384, 1}};
+  for (const auto& s : rig_shapes) {
+    int p2l = 2, p2r = 2;
+    while (p2l < s[0]) p2l <<= 1;
+    while (p2r < s[1]) p2r <<= 1;
+    printf("rig_layout %d %d %d %zu\n", s[0], s[1], s[2], orbx::side::win::rig_layout(s[0], s[1], s[2], p2l, p2r, true).fixed);
   }
   printf("lds_max %d\n", orbx::side::win::kLdsMax);
   return g_bad ? 1 : 0;

@@ -98,35 +98,6 @@ def test_the_planted_cases_are_what_they_claim(case):
     assert len(c["frames"]) <= 8 and len(c["items"]) <= 8
 
 
-def test_the_room_the_gpu_test_states_is_the_layouts():
-    """lds_bytes() is rig_layout(...).fixed of the source, piece by piece."""
-    import os
-    import re
-    from orb_slam3_modified_amd import build
-    from orb_slam3_modified_amd.rigmatch import lds_bytes
-    src = open(os.path.join(build.CSRC, build.RIGMATCH_SOURCE)).read()
-    body = src[src.index("inline RigLay rig_layout("):]
-    adds = re.findall(r"= add\((.*?)\);", body[:body.index("l.cand = o;")])
-    assert len(adds) == 10
-    cap_l, cap_r, mcap, p2l, p2r, lds = rc.CAP_L, rc.CAP_R, rc.MCAP, 128, 128, True   # noqa: F841
-    env = dict(cap_l=cap_l, cap_r=cap_r, mcap=mcap, p2l=p2l, p2r=p2r, kRecBytes=16, kCells=64 * 48)
-    total = 0
-    for a in adds:
-        expr = a.replace("(size_t)", "").replace("lds ? ", "").replace(" : 0", "")
-        total += (int(eval(expr, {}, env)) + 15) & ~15
-    assert total == lds_bytes(cap_l, cap_r, mcap)
-    # plan_paths (csrc/side/orbx_handle.h) on the three limits the GPU test creates its handles with: the LDS path with room for
-    # SMALL_ROOM candidates under the lowered limit, more than every item's lists under the default one, the global path under 0
-    from orb_slam3_modified_amd.rigmatch import LDS_MAX
-    handle = open(os.path.join(build.CSRC, "side", "orbx_handle.h")).read()
-    assert "p->in_lds = fixed_lds + 4 * (size_t)longest <= limit;" in handle and "(int)((limit - fixed_lds) / 4)" in handle
-
-    def plan(lds_limit):
-        limit = lds_limit & ~15
-        return (limit - total) // 4 if total + 4 * rc.SLOTS <= limit else None   # the room on the LDS path, None: the global path
-    assert plan(total + 4 * rc.SMALL_ROOM) == rc.SMALL_ROOM and plan(0) is None and plan(LDS_MAX) > 8 * rc.SMALL_ROOM
-
-
 # ---- the model held to the reference's recorded output (tests/golden/matcher_world_ref.txt.gz) on the dumped rig scenarios
 def _model_on(rec):
     """{record name: (ret, ids)} of the model on a dump's three golden scenarios."""
