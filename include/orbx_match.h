@@ -2,6 +2,7 @@
  * against KeyFrame; the single-camera branches) for P (frame, frame) pairs at once, on the descriptors, keypoints and FeatureVectors a batch
  * extraction and orbx_bow_transform_batch_device left in HBM.  Not part of the drop-in boundary (include/orbx.h): these entry points live in
  * liborbx_match.so.  The library reads plain device arrays only; it takes nothing from a context or a vocabulary.
+ * The two-camera rig branches (Nleft != -1) are include/orbx_rigbow.h's (liborbx_rigbow.so).
  *
  * The specification is the reference's loop.  For pair p = (ia, ib), side A holds the queries (the "keyframe"), side B the frame whose
  * features are taken:

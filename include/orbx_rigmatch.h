@@ -5,7 +5,8 @@
  * boundary (include/orbx.h): these entry points live in liborbx_rigmatch.so.  The library reads plain device arrays only; it takes nothing
  * from a context.  The Nleft == -1 forms are include/orbx_localmatch.h's and include/orbx_lastmatch.h's.
  *
- * Out of scope: the rig blocks of the relocalization SearchByProjection (:1889), of Fuse (bRight), SearchForTriangulation and SearchByBoW;
+ * The rig block of SearchByBoW (:296-323, :357-386) and the stacked rig frame it needs are include/orbx_rigbow.h's (liborbx_rigbow.so).
+ * Out of scope: the rig blocks of the relocalization SearchByProjection (:1889), of Fuse (bRight) and of SearchForTriangulation;
  * the KannalaBrandt8 projections that produce the rows (Frame::isInFrustum's two-camera part, Trl * x3Dc at :1795-1796): the caller's.
  *
  * The rig side.  Two frame sides in orbx_localmatch_side's layout with capacities of their own, cap_l and cap_r; the keypoints are the RAW

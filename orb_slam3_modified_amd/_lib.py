@@ -33,6 +33,7 @@ FRUSTUM_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_frustum.so")
 PROJECT_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_project.so")         # the LastFrame, relocalization and Fuse projections (include/orbx_project.h)
 SIM3_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_sim3.so")               # LoopClosing's Sim3 projections and agreement pass (include/orbx_sim3.h)
 RIGMATCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_rigmatch.so")       # the two-camera rig blocks of the two Tracking matchers (include/orbx_rigmatch.h)
+RIGBOW_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_rigbow.so")           # the rig block of SearchByBoW and the stacked rig frame (include/orbx_rigbow.h)
 
 ORBX_OK, ORBX_E_INVALID, ORBX_E_EMPTY, ORBX_E_DEVICE, ORBX_E_CAPACITY, ORBX_E_FORMAT = 0, -1, -2, -3, -4, -5
 NUM_KERNELS = 6
@@ -627,10 +628,40 @@ def rigmatch_lib(path: str = RIGMATCH_LIB_PATH) -> C.CDLL:
     return M
 
 
+class OrbxRigBowRig(C.Structure):
+    """orbx_rigbow_rig (include/orbx_rigbow.h)."""
+    _fields_ = [("d_kps_l", C.c_void_p), ("d_desc_l", C.c_void_p), ("d_counts_l", C.c_void_p), ("d_kps_r", C.c_void_p), ("d_desc_r", C.c_void_p),
+                ("d_counts_r", C.c_void_p), ("nframes", C.c_int), ("cap_l", C.c_int), ("cap_r", C.c_int)]
+
+
+class OrbxRigBowSide(C.Structure):
+    """orbx_rigbow_side (include/orbx_rigbow.h)."""
+    _fields_ = [("d_kps", C.c_void_p), ("d_desc", C.c_void_p), ("d_counts", C.c_void_p), ("d_fv_node", C.c_void_p), ("d_fv_ptr", C.c_void_p),
+                ("d_fv_feat", C.c_void_p), ("d_fv_n", C.c_void_p), ("d_valid", C.c_void_p), ("d_nleft", C.c_void_p), ("nframes", C.c_int),
+                ("capacity", C.c_int)]
+
+
+def rigbow_lib(path: str = RIGBOW_LIB_PATH) -> C.CDLL:
+    """liborbx_rigbow.so.  `_orbx_rigbow_symbols`: every name of include/orbx_rigbow.h, bound here with its signature.  `path`: a timing
+    build of the same source."""
+    vp, i32, f32, sp, rp = C.c_void_p, C.c_int, C.c_float, C.POINTER(OrbxRigBowSide), C.POINTER(OrbxRigBowRig)
+    sig = {
+        "orbx_rigbow_create": (i32, [C.POINTER(vp), i32]),
+        "orbx_rigbow_destroy": (None, [vp]),
+        "orbx_rigbow_last_error": (C.c_char_p, [vp]),
+        "orbx_rigbow_stack_device": (i32, [vp, rp, i32, vp, vp, vp, vp, vp]),
+        "orbx_rigbow_pairs_device": (i32, [vp, sp, sp, vp, i32, i32, f32, i32, vp, vp, vp, vp]),
+        "orbx_rigbow_pairs": (i32, [vp, sp, sp, vp, i32, i32, f32, i32, vp, vp, vp]),
+    }
+    M = _load_side(path, sig)
+    M._orbx_rigbow_symbols = tuple(sig)
+    return M
+
+
 class SideHandle:
     """A handle of a side library whose entry points are <prefix>_create / _destroy / _last_error (StereoBatch, BowBatch, MatchBatch,
     InitMatchBatch, TriMatchBatch, FuseBatch, DistinctBatch, ScoreBatch, FisheyeBatch, LocalMatchBatch, LastMatchBatch, ProjMatchBatch,
-    PlaceBatch, PlaceIndex, FrustumBatch, ProjectBatch, Sim3Batch, RigMatchBatch)."""
+    PlaceBatch, PlaceIndex, FrustumBatch, ProjectBatch, Sim3Batch, RigMatchBatch, RigBowBatch)."""
 
     def __init__(self, library: C.CDLL, prefix: str, *create_args):
         self._L, self._prefix, self._h = library, prefix, C.c_void_p(0)
