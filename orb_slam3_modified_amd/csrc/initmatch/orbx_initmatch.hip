@@ -307,18 +307,7 @@ __global__ __launch_bounds__(kThreads) void k_init_pairs(Args g) {
         }
       }
       __syncthreads();
-      if (tid == 0) {                      // ComputeThreeMaxima, src/ORBmatcher.cc:2012-2053
-        int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
-        for (int i = 0; i < 30; i++) {
-          const int s = s_hist[i];
-          if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-          else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-          else if (s > max3) { max3 = s; ind3 = i; }
-        }
-        if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-        else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
-        s_ind[0] = ind1; s_ind[1] = ind2; s_ind[2] = ind3;
-      }
+      if (tid == 0) three_maxima(s_hist, s_ind);
       __syncthreads();
       i1 = s_ind[0]; i2 = s_ind[1]; i3 = s_ind[2];
     }

@@ -1,10 +1,11 @@
 // The device helpers the side libraries' matching kernels share: descriptors and Hamming distances, the wave minimum, the 32-bit top-2
 // keys, a chain's relaxed loads and stores, the rotation bin, the keypoint field reader, the LDS-DMA staging, a frame grid's record, a work
-// list's pop and the workgroup scan.  Every source below csrc/ that includes this file is a user; the frame grid and the window of the
-// four chained projection matchers are built on it in orbx_window_device.h.  Device code only; it sits below csrc/, outside
-// kernels_hash().  A kernel's file imports the names with `using namespace orbx::side::dev;` inside its anonymous namespace.
-// ComputeThreeMaxima and the trip loop's three-reduction merge stay written out in k_match_pairs and k_init_pairs: as functions of this
-// header they change those kernels' instruction streams (the compiler unrolls and schedules them differently).
+// list's pop, the workgroup scan and, for k_tri_pairs and k_init_pairs, the FeatureVector node intersection and ComputeThreeMaxima.
+// Every source below csrc/ that includes this file is a user; the frame grid and the window of the four chained projection matchers
+// are built on it in orbx_window_device.h.  Device code only; it sits below csrc/, outside kernels_hash().  A kernel's file imports the
+// names with `using namespace orbx::side::dev;` inside its anonymous namespace.
+// k_match_pairs and k_rigbow_pairs keep their own text of both: as one core their one-node trip loop measured 1.3 to 2.4 % slower
+// (profiles/bowpair_core_refactor.txt).  The trip loop's three-reduction merge stays written out where it is used.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -75,6 +76,24 @@ __device__ __forceinline__ int rot_bin(float angle_a, float angle_b) {
   return bin == 30 ? 0 : bin;
 }
 
+// ComputeThreeMaxima (src/ORBmatcher.cc:2012-2053) on one lane: the three fullest of hist's 30 bins into ind[0 .. 2], -1 as there
+__device__ __forceinline__ void three_maxima(const int* hist, int* ind) {
+  int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
+  int h[30];                               // all bins first: one wait on the one lane the workgroup waits for
+#pragma unroll
+  for (int i = 0; i < 30; i++) h[i] = hist[i];
+#pragma unroll
+  for (int i = 0; i < 30; i++) {
+    const int s = h[i];
+    if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
+    else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
+    else if (s > max3) { max3 = s; ind3 = i; }
+  }
+  if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
+  else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
+  ind[0] = ind1; ind[1] = ind2; ind[2] = ind3;
+}
+
 // field `field` (an offsetof) of keypoint i of a keypoint array
 template <class T>
 __device__ __forceinline__ T kp_field(const uint8_t* kps, size_t i, size_t field) { return *(const T*)(kps + i * sizeof(orbx_keypoint) + field); }
@@ -92,6 +111,24 @@ __device__ __forceinline__ void stage_dma(uint8_t* dst, const uint8_t* src, int 
 }
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+
+// the nodes two FeatureVectors share, a thread per A node: emit(a0, a1, b0, b1), the two feature ranges (clamped), when neither is empty
+template <int THREADS, class E>
+__device__ __forceinline__ void common_nodes(const uint32_t* nodeA, const int32_t* pA, int kA, int totA, const uint32_t* nodeB, const int32_t* pB, int kB,
+                                             int totB, E emit) {
+  for (int ja = threadIdx.x; ja < kA; ja += THREADS) {
+    const uint32_t node = nodeA[ja];
+    int lo = 0, hi = kB;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (nodeB[mid] < node) lo = mid + 1; else hi = mid;
+    }
+    if (lo < kB && nodeB[lo] == node) {
+      const int a0 = clampi(pA[ja], 0, totA), a1 = clampi(pA[ja + 1], 0, totA), b0 = clampi(pB[lo], 0, totB), b1 = clampi(pB[lo + 1], 0, totB);
+      if (a1 > a0 && b1 > b0) emit(a0, a1, b0, b1);
+    }
+  }
+}
 
 // the wave's next item of a work list: lane 0 takes it from the LDS counter, wave-uniform
 __device__ __forceinline__ int next_work(int* s_next) {

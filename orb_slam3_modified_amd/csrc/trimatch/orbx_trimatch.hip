@@ -9,8 +9,8 @@
 //              match row in LDS -- 32 (capA + capB) + 16 (min(capA, capB) + capA / 16 + 1) + 4 (2 capA + capB) bytes.  Global path (pairs
 //              that need more LDS than the handle's limit): the descriptors where they lie, lists and work list in the workgroup's slice
 //              of the handle's scratch, the match row in the caller's d_matches12.
-//   intersect  a thread per A node: binary search in B's node list; a common node becomes chunks of at most kChunk queries
-//              (a0, a1, b0, b1) in a work list.
+//   intersect  common_nodes (orbx_pair_device.h), a thread per A node: binary search in B's node list; a common node becomes chunks of
+//              at most kChunk queries (a0, a1, b0, b1) in a work list.
 //   queries    there is no chain (vbMatched2 is never written): all waves take chunks from the list (an LDS counter) and nothing orders them.
 //              Lanes take B candidates:
 //                nb <= 64: lane j keeps candidate j -- descriptor in 8 registers, flags in one -- over the chunk's queries;
@@ -18,7 +18,7 @@
 //              The A descriptor is wave-uniform.  A lane with dist <= 50 evaluates the two float gates (a, b, c of the epipolar line depend
 //              on the query alone) and holds the key dist << 16 | (0xFFFF - position); every other lane holds INT_MAX.  One DPP
 //              min-reduction gives the winner: the smallest distance, the LAST position among its holders.
-//   filter     after a barrier: a thread per A feature adds its match's bin to an LDS histogram; one lane runs ComputeThreeMaxima; a thread
+//   filter     after a barrier: a thread per A feature adds its match's bin to an LDS histogram; one lane runs three_maxima; a thread
 //              per A feature recomputes its bin, drops the match when the bin lost, writes matches12 and counts.
 // The gates are compiled with -ffp-contract=off: every float operation is rounded by itself, as the specification states them.
 #include <hip/hip_runtime.h>
@@ -183,28 +183,12 @@ __global__ __launch_bounds__(kThreads) void k_tri_pairs(Args g) {
     if (s_bad) { fail_row(g, p, o12); continue; }
 
     // ---- the nodes both frames have, cut into chunks of queries
-    {
-      const uint32_t* const nodeA = g.a.fv_node + oA;
-      const uint32_t* const nodeB = g.b.fv_node + oB;
-      for (int ja = tid; ja < kA; ja += kThreads) {
-        const uint32_t node = nodeA[ja];
-        int lo = 0, hi = kB;
-        while (lo < hi) {
-          const int mid = (lo + hi) >> 1;
-          if (nodeB[mid] < node) lo = mid + 1; else hi = mid;
-        }
-        if (lo < kB && nodeB[lo] == node) {
-          const int a0 = clampi(pA[ja], 0, totA), a1 = clampi(pA[ja + 1], 0, totA);
-          const int b0 = clampi(pB[lo], 0, totB), b1 = clampi(pB[lo + 1], 0, totB);
-          if (a1 > a0 && b1 > b0) {
-            const int nc = (a1 - a0 + kChunk - 1) / kChunk;
-            const int k = atomicAdd(&s_cnt, nc);
-            for (int c = 0; c < nc; c++)
-              if (k + c < maxw) work[k + c] = make_int4(a0 + c * kChunk, min(a1, a0 + (c + 1) * kChunk), b0, b1);
-          }
-        }
-      }
-    }
+    common_nodes<kThreads>(g.a.fv_node + oA, pA, kA, totA, g.b.fv_node + oB, pB, kB, totB, [&](int a0, int a1, int b0, int b1) {
+      const int nc = (a1 - a0 + kChunk - 1) / kChunk;
+      const int k = atomicAdd(&s_cnt, nc);
+      for (int c = 0; c < nc; c++)
+        if (k + c < maxw) work[k + c] = make_int4(a0 + c * kChunk, min(a1, a0 + (c + 1) * kChunk), b0, b1);
+    });
     __syncthreads();
     const int nwork = min(s_cnt, maxw);
     Geom G;
@@ -271,18 +255,7 @@ __global__ __launch_bounds__(kThreads) void k_tri_pairs(Args g) {
         }
       }
       __syncthreads();
-      if (tid == 0) {                      // ComputeThreeMaxima, src/ORBmatcher.cc:2012-2053
-        int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
-        for (int i = 0; i < 30; i++) {
-          const int s = s_hist[i];
-          if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-          else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-          else if (s > max3) { max3 = s; ind3 = i; }
-        }
-        if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-        else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
-        s_ind[0] = ind1; s_ind[1] = ind2; s_ind[2] = ind3;
-      }
+      if (tid == 0) three_maxima(s_hist, s_ind);
       __syncthreads();
       i1 = s_ind[0]; i2 = s_ind[1]; i3 = s_ind[2];
     }

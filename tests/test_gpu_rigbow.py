@@ -132,24 +132,32 @@ def test_the_stacker_equals_the_model():
 
 
 @pytest.mark.parametrize("mode", [FRAME, KEYFRAMES])
-def test_single_camera_frames_equal_match_batch(mode):
+def test_single_camera_frames_equal_match_batch(monkeypatch, mode):
     """nleft = -1 everywhere (as an array and as NULL): the bytes of MatchBatch on the same arrays, tests/match_batch_cases.py's batch in
-    two calls."""
+    two calls.  k_rigbow_pairs is k_match_pairs' text with a second camera: this holds on each of the four paths (LDS or global,
+    register path or trip loop), both handles created on the same one."""
     from orb_slam3_modified_amd.match import MatchBatch, MatchSide
     c = mc.build()
-    mb, rb = MatchBatch(0), RigBowBatch(0)
     c["nleft"] = np.full(mc.K, -1, np.int32)
-    for valid in (True, False):
-        ms = MatchSide(c["kps"], c["desc"], c["counts"], c["fv_node"], c["fv_ptr"], c["fv_feat"], c["fv_n"], mc.K, mc.CAP, c["valid"] if valid else None)
-        for pairs in (mc.PAIRS[:8], mc.PAIRS[8:]):
-            w = mb.bow_pairs(ms, ms, pairs, mode, mc.RATIO, True)
-            for nleft in (True, False):
-                r = rb.bow_pairs(_side(c, valid, nleft), _side(c, valid, nleft), pairs, mode, mc.RATIO, True)
-                assert np.array_equal(r.nmatches, w.nmatches) and np.array_equal(r.b2a, w.b2a), (mode, valid, nleft)
-                assert np.array_equal(r.a2b[:, :, 0], w.a2b) and (r.a2b[:, :, 1] == -1).all(), (mode, valid, nleft)
-            assert (w.nmatches > 0).any()
-    mb.close()
-    rb.close()
+    for path, env in PATHS.items():
+        menv = {k_.replace("ORBX_RIGBOW_", "ORBX_MATCH_"): v_ for k_, v_ in env.items()}
+        for k_, v_ in menv.items():
+            monkeypatch.setenv(k_, v_)
+        mb = MatchBatch(0)
+        for k_ in menv:
+            monkeypatch.delenv(k_)
+        rb = _handle(monkeypatch, env)
+        for valid in (True, False):
+            ms = MatchSide(c["kps"], c["desc"], c["counts"], c["fv_node"], c["fv_ptr"], c["fv_feat"], c["fv_n"], mc.K, mc.CAP, c["valid"] if valid else None)
+            for pairs in (mc.PAIRS[:8], mc.PAIRS[8:]):
+                w = mb.bow_pairs(ms, ms, pairs, mode, mc.RATIO, True)
+                for nleft in (True, False):
+                    r = rb.bow_pairs(_side(c, valid, nleft), _side(c, valid, nleft), pairs, mode, mc.RATIO, True)
+                    assert np.array_equal(r.nmatches, w.nmatches) and np.array_equal(r.b2a, w.b2a), (path, mode, valid, nleft)
+                    assert np.array_equal(r.a2b[:, :, 0], w.a2b) and (r.a2b[:, :, 1] == -1).all(), (path, mode, valid, nleft)
+                assert (w.nmatches > 0).any()
+        mb.close()
+        rb.close()
 
 
 def test_device_resident_chain(tmp_path):
