@@ -89,6 +89,7 @@ RIGMATCH_SOURCE = os.path.join("rigmatch", "orbx_rigmatch.hip")
 RIGBOW_OUT = os.path.join(os.path.dirname(OUT), "liborbx_rigbow.so")
 RIGBOW_SOURCE = os.path.join("rigbow", "orbx_rigbow.hip")
 FRONT_CORE = (os.path.join("side", "orbx_front_device.h"), os.path.join("side", "orbx_front_host.h"))   # what the three projection fronts share
+PAIR_CORE = (os.path.join("side", "orbx_pair_device.h"), os.path.join("side", "orbx_pair_host.h"))   # what the four pair matchers share
 
 
 class Lib(NamedTuple):
@@ -104,9 +105,9 @@ LIBS = (Lib(OUT, tuple(SOURCES)),
         Lib(TRAIN_OUT, (TRAIN_SOURCE,), product=True),
         Lib(STEREO_OUT, (STEREO_SOURCE,), hidden=True, product=True),
         Lib(BOW_OUT, (BOW_SOURCE,), hidden=True, product=True),
-        Lib(MATCH_OUT, (MATCH_SOURCE,), hidden=True, product=True),
-        Lib(INITMATCH_OUT, (INITMATCH_SOURCE,), hidden=True, product=True),
-        Lib(TRIMATCH_OUT, (TRIMATCH_SOURCE,), hidden=True, product=True),
+        Lib(MATCH_OUT, (MATCH_SOURCE,), hidden=True, product=True, deps=PAIR_CORE),
+        Lib(INITMATCH_OUT, (INITMATCH_SOURCE,), hidden=True, product=True, deps=PAIR_CORE),
+        Lib(TRIMATCH_OUT, (TRIMATCH_SOURCE,), hidden=True, product=True, deps=PAIR_CORE),
         Lib(FUSE_OUT, (FUSE_SOURCE,), hidden=True, product=True),
         Lib(MPDESC_OUT, (MPDESC_SOURCE,), hidden=True, product=True),
         Lib(SCORE_OUT, (SCORE_SOURCE,), hidden=True),
@@ -120,7 +121,7 @@ LIBS = (Lib(OUT, tuple(SOURCES)),
         Lib(PROJECT_OUT, (PROJECT_SOURCE,), hidden=True, deps=FRONT_CORE),
         Lib(SIM3_OUT, (SIM3_SOURCE,), hidden=True, deps=FRONT_CORE),
         Lib(RIGMATCH_OUT, (RIGMATCH_SOURCE,), hidden=True, deps=WINDOW_CORE),
-        Lib(RIGBOW_OUT, (RIGBOW_SOURCE,), hidden=True))
+        Lib(RIGBOW_OUT, (RIGBOW_SOURCE,), hidden=True, deps=PAIR_CORE))
 HEADERS = ("orbx.h", "orbx_debug.h", "orbx_train.h", "orbx_stereo.h", "orbx_bow.h", "orbx_match.h", "orbx_initmatch.h", "orbx_trimatch.h",
            "orbx_fuse.h", "orbx_mpdesc.h", "orbx_score.h", "orbx_fisheye.h", "orbx_localmatch.h", "orbx_lastmatch.h",
            "orbx_projmatch.h", "orbx_place.h", "orbx_placeindex.h", "orbx_frustum.h", "orbx_project.h", "orbx_sim3.h", "orbx_rigmatch.h",

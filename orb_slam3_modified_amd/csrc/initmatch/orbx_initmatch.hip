@@ -26,6 +26,7 @@
 
 #include "../side/orbx_handle.h"
 #include "../side/orbx_pair_device.h"
+#include "../side/orbx_pair_host.h"
 #include "../../../include/orbx_initmatch.h"
 
 namespace {
@@ -33,9 +34,7 @@ namespace {
 using namespace orbx::side::dev;          // ld / st on the chain's state: written by one lane, read by the wave's other lanes in the next step
 
 constexpr int kThreads = 512;             // 8 waves
-constexpr int kLdsMax = 152 * 1024;       // dynamic LDS of one workgroup (160 KiB per CU, the static part is below 4 KiB)
-constexpr int kMaxBlocks = 1024;          // workgroups of one launch on the LDS path
-constexpr int kGlobalBlocks = 256;        // ... on the global path: each owns one slice of the scratch
+constexpr int kGlobalBlocks = 256;        // workgroups of one launch on the global path (kMaxBlocks on the LDS path): each owns one slice of the scratch
 constexpr int kGlobalRoom = 64 * 1024;    // candidates of one chunk on the global path (at least capB)
 constexpr int kMaxCap = 32768;            // a key holds a 15-bit index, a candidate a 16-bit one
 constexpr int kCols = 64, kRows = 48, kCells = kCols * kRows;
@@ -339,35 +338,21 @@ __global__ __launch_bounds__(kThreads) void k_init_pairs(Args g) {
 
 }  // namespace
 
-struct orbx_initmatch : orbx::side::Handle {   // scratch: per workgroup the global path's arrays
-  int lds_limit = kLdsMax;                     // ORBX_INITMATCH_LDS at create
-};
+struct orbx_initmatch : orbx::side::pair::PairHandle {};   // scratch: per workgroup the global path's arrays
 
 namespace {
 
 using namespace orbx::side;
-
-const char* side_problem(const orbx_initmatch_side* s) {
-  if (!s) return "null side";
-  if (s->nframes < 1 || s->capacity < 1) return "nframes and capacity must be at least 1";
-  if (s->capacity > kMaxCap) return "capacity above 32768";
-  if (!s->d_kps || !s->d_desc || !s->d_counts) return "null buffer in a side";
-  return nullptr;
-}
+using namespace orbx::side::pair;
 
 // what both forms check before anything is copied or launched
 int check_call(orbx_initmatch* m, const char* who, const orbx_initmatch_side* a, const orbx_initmatch_side* b, const void* pairs, int npairs,
                const float* bounds, int window, const void* m12, const void* nm) {
-  for (const orbx_initmatch_side* s : {a, b})
-    if (const char* e = side_problem(s)) return fail(m, ORBX_E_INVALID, std::string(who) + e);
-  if (!pairs || !m12 || !nm || !bounds) return fail(m, ORBX_E_INVALID, std::string(who) + "null pairs, bounds, matches12 or nmatches");
-  if (npairs < 1) return fail(m, ORBX_E_INVALID, std::string(who) + "npairs = " + std::to_string(npairs) + " (at least 1)");
+  int rc = check_sides<false>(m, who, a, b, kMaxCap, "capacity above 32768", pairs && m12 && nm && bounds, "pairs, bounds, matches12 or nmatches");
+  if (rc != ORBX_OK || (rc = check_npairs(m, who, npairs)) != ORBX_OK) return rc;
   if (window < 0) return fail(m, ORBX_E_INVALID, std::string(who) + "window_size = " + std::to_string(window) + " (at least 0)");
   if (!(bounds[2] > bounds[0]) || !(bounds[3] > bounds[1])) return fail(m, ORBX_E_INVALID, std::string(who) + "bounds: max must be above min");
-  if ((long long)npairs * std::max(a->capacity, b->capacity) * 2 > (long long)INT_MAX || (long long)a->nframes * a->capacity > (long long)INT_MAX ||
-      (long long)b->nframes * b->capacity > (long long)INT_MAX)
-    return fail(m, ORBX_E_INVALID, std::string(who) + "npairs * capacity or nframes * capacity exceeds INT_MAX");
-  return ORBX_OK;
+  return check_sizes<false>(m, who, a, b, npairs, 2LL * std::max(a->capacity, b->capacity), "npairs * capacity");
 }
 
 }  // namespace
@@ -376,8 +361,7 @@ extern "C" {
 
 int orbx_initmatch_create(orbx_initmatch** out, int device) {
   return create_handle(out, device, "orbx_initmatch_create", orbx_initmatch_destroy, [](orbx_initmatch* m) {
-    m->lds_limit = env_int("ORBX_INITMATCH_LDS", 0, kLdsMax, kLdsMax);
-    return allow_lds((const void*)k_init_pairs<true>, kLdsMax);
+    return open_pair(m, "ORBX_INITMATCH_LDS", nullptr, (const void*)k_init_pairs<true>);
   });
 }
 
@@ -399,23 +383,18 @@ int orbx_initmatch_pairs_device(orbx_initmatch* m, const orbx_initmatch_side* a,
   const int capA = a->capacity, capB = b->capacity;
   int p2 = 2;
   while (p2 < capB) p2 <<= 1;
-  Paths path;                              // one query's longest list is capB candidates
+  Paths path;                              // one query's longest list is capB candidates; the global path's scratch is grown here
   if ((rc = plan_paths(m, m->lds_limit, layout(capA, capB, p2, true).fixed, layout(capA, capB, p2, false).fixed, capB, npairs,
                        {kMaxBlocks, kGlobalBlocks, kGlobalRoom}, &path)) != ORBX_OK) return rc;
   Args g;
   g.a = {(const uint8_t*)a->d_kps, a->d_desc, a->d_counts, a->nframes, capA};
   g.b = {(const uint8_t*)b->d_kps, b->d_desc, b->d_counts, b->nframes, capB};
   g.pairs = d_pairs; g.prev = d_prev_xy; g.m12 = d_matches12; g.m21 = d_matches21; g.nm = d_nmatches;
-  g.scratch = path.in_lds ? nullptr : m->scratch.p; g.scratch_stride = path.scratch_stride;
   g.npairs = npairs; g.p2 = p2; g.room = path.room; g.check_ori = check_orientation != 0;
   g.minX = bounds[0]; g.minY = bounds[1];
   g.invW = (float)kCols / (bounds[2] - bounds[0]); g.invH = (float)kRows / (bounds[3] - bounds[1]);
   g.r = (float)window_size; g.ratio = nn_ratio;
-  hipStream_t st = stream ? (hipStream_t)stream : m->st;
-  if ((rc = wait_previous(m, st)) != ORBX_OK) return rc;
-  if (path.in_lds) hipLaunchKernelGGL(k_init_pairs<true>, dim3((unsigned)path.blocks), dim3(kThreads), path.lds_bytes, st, g);
-  else hipLaunchKernelGGL(k_init_pairs<false>, dim3((unsigned)path.blocks), dim3(kThreads), 0, st, g);
-  return record_call(m, st);
+  return launch(m, path.in_lds, path.lds_bytes, path.scratch_stride, path.blocks, kThreads, g, k_init_pairs<true>, k_init_pairs<false>, stream);
 }
 
 int orbx_initmatch_pairs(orbx_initmatch* m, const orbx_initmatch_side* a, const orbx_initmatch_side* b, const int32_t* pairs, int npairs,
@@ -425,16 +404,9 @@ int orbx_initmatch_pairs(orbx_initmatch* m, const orbx_initmatch_side* a, const 
   const char* who = "orbx_initmatch_pairs: ";
   int rc = check_call(m, who, a, b, pairs, npairs, bounds, window_size, matches12, nmatches);
   if (rc != ORBX_OK) return rc;
-  const bool same = a == b || std::memcmp(a, b, sizeof(*a)) == 0;   // one batch on both sides is staged once
+  const auto arrays = side_arrays<false, orbx_initmatch_side>();
   Stager io;
-  struct Off { size_t kps, desc, counts; } off[2];
-  const orbx_initmatch_side* sides[2] = {a, b};
-  for (int s = 0; s < (same ? 1 : 2); s++) {
-    const orbx_initmatch_side* h = sides[s];
-    const size_t nf = (size_t)h->nframes, nk = nf * h->capacity;
-    off[s] = {io.in(h->d_kps, nk * sizeof(orbx_keypoint)), io.in(h->d_desc, nk * 32), io.in(h->d_counts, nf * 8)};
-  }
-  if (same) off[1] = off[0];
+  const StagedSides off = stage_sides(io, a, b, arrays);
   const size_t o_pairs = io.in(pairs, (size_t)npairs * 8);
   const size_t n12 = (size_t)npairs * a->capacity * 4, n21 = (size_t)npairs * b->capacity * 4, nprev = prev_xy ? n12 * 2 : 0;
   const size_t o_prev = io.out(prev_xy, nprev, true), o_12 = io.out(matches12, n12), o_21 = io.out(matches21, n21),
@@ -442,8 +414,7 @@ int orbx_initmatch_pairs(orbx_initmatch* m, const orbx_initmatch_side* a, const 
   if ((rc = upload(m, io)) != ORBX_OK) return rc;
   uint8_t* d = m->io.p;
   orbx_initmatch_side ds[2];
-  for (int s = 0; s < 2; s++)
-    ds[s] = {(const orbx_keypoint*)(d + off[s].kps), d + off[s].desc, (const int32_t*)(d + off[s].counts), sides[s]->nframes, sides[s]->capacity};
+  device_sides(d, off, a, b, arrays, ds);
   rc = orbx_initmatch_pairs_device(m, &ds[0], &ds[1], (const int32_t*)(d + o_pairs), npairs, bounds, window_size, nn_ratio, check_orientation,
                                    prev_xy ? (float*)(d + o_prev) : nullptr, (int32_t*)(d + o_12), (int32_t*)(d + o_21), (int32_t*)(d + o_nm), m->st);
   if (rc != ORBX_OK) return rc;

@@ -27,6 +27,7 @@
 
 #include "../side/orbx_handle.h"
 #include "../side/orbx_pair_device.h"
+#include "../side/orbx_pair_host.h"
 #include "../../../include/orbx_match.h"
 
 namespace {
@@ -34,9 +35,6 @@ namespace {
 using namespace orbx::side::dev;           // ld / st on B's match row: written by one lane, read by the wave's other lanes in the next step
 
 constexpr int kThreads = 512;             // 8 waves
-constexpr int kLdsMax = 152 * 1024;       // dynamic LDS of one workgroup (160 KiB per CU, the static part is below 1 KiB)
-constexpr int kMaxBlocks = 1024;          // workgroups of one launch: each owns one slice of the scratch
-constexpr int kWaveNode = 64;
 
 struct Side {
   const uint8_t* kps; const uint8_t* desc; const int32_t* counts; const uint32_t* fv_node; const int32_t* fv_ptr; const uint32_t* fv_feat;
@@ -271,21 +269,12 @@ __global__ __launch_bounds__(kThreads) void k_match_pairs(Args g) {
 
 }  // namespace
 
-struct orbx_match : orbx::side::Handle {   // scratch: per workgroup the global path's work list and match row
-  int lds_limit = kLdsMax;                 // ORBX_MATCH_LDS at create
-  int wave_node = kWaveNode;               // ORBX_MATCH_WAVE_NODE at create
-};
+struct orbx_match : orbx::side::pair::PairHandle {};   // scratch: per workgroup the global path's work list and match row
 
 namespace {
 
 using namespace orbx::side;
-
-const char* side_problem(const orbx_match_side* s) {
-  if (!s) return "null side";
-  if (s->nframes < 1 || s->capacity < 1) return "nframes and capacity must be at least 1";
-  if (!s->d_kps || !s->d_desc || !s->d_counts || !s->d_fv_node || !s->d_fv_ptr || !s->d_fv_feat || !s->d_fv_n) return "null buffer in a side";
-  return nullptr;
-}
+using namespace orbx::side::pair;
 
 Side to_side(const orbx_match_side* s) {
   return {(const uint8_t*)s->d_kps, s->d_desc, s->d_counts, s->d_fv_node, s->d_fv_ptr, s->d_fv_feat, s->d_fv_n, s->d_valid, s->nframes, s->capacity};
@@ -294,16 +283,12 @@ Side to_side(const orbx_match_side* s) {
 // what both forms check before anything is copied or launched
 int check_call(orbx_match* m, const char* who, const orbx_match_side* a, const orbx_match_side* b, const void* pairs, int npairs, int mode,
                const void* b2a, const void* a2b, const void* nm) {
-  for (const orbx_match_side* s : {a, b})
-    if (const char* e = side_problem(s)) return fail(m, ORBX_E_INVALID, std::string(who) + e);
-  if (!pairs || !nm) return fail(m, ORBX_E_INVALID, std::string(who) + "null pairs or nmatches");
+  int rc = check_sides<true>(m, who, a, b, 0, nullptr, pairs && nm, "pairs or nmatches");
+  if (rc != ORBX_OK) return rc;
   if (!b2a && !a2b) return fail(m, ORBX_E_INVALID, std::string(who) + "both match arrays are null");
-  if (npairs < 1) return fail(m, ORBX_E_INVALID, std::string(who) + "npairs = " + std::to_string(npairs) + " (at least 1)");
+  if ((rc = check_npairs(m, who, npairs)) != ORBX_OK) return rc;
   if (mode != ORBX_MATCH_FRAME && mode != ORBX_MATCH_KEYFRAMES) return fail(m, ORBX_E_INVALID, std::string(who) + "unknown mode " + std::to_string(mode));
-  if ((long long)npairs * std::max(a->capacity, b->capacity) > (long long)INT_MAX || (long long)a->nframes * (a->capacity + 1) > (long long)INT_MAX ||
-      (long long)b->nframes * (b->capacity + 1) > (long long)INT_MAX)
-    return fail(m, ORBX_E_INVALID, std::string(who) + "npairs * capacity or nframes * capacity exceeds INT_MAX");
-  return ORBX_OK;
+  return check_sizes<true>(m, who, a, b, npairs, std::max(a->capacity, b->capacity), "npairs * capacity");
 }
 
 }  // namespace
@@ -312,9 +297,7 @@ extern "C" {
 
 int orbx_match_create(orbx_match** out, int device) {
   return create_handle(out, device, "orbx_match_create", orbx_match_destroy, [](orbx_match* m) {
-    m->lds_limit = env_int("ORBX_MATCH_LDS", 0, kLdsMax, kLdsMax);
-    m->wave_node = env_int("ORBX_MATCH_WAVE_NODE", 0, kWaveNode, kWaveNode);
-    return allow_lds((const void*)k_match_pairs<true>, kLdsMax);
+    return open_pair(m, "ORBX_MATCH_LDS", "ORBX_MATCH_WAVE_NODE", (const void*)k_match_pairs<true>);
   });
 }
 
@@ -334,24 +317,13 @@ int orbx_match_bow_pairs_device(orbx_match* m, const orbx_match_side* a, const o
   ORBX_SIDE_HIP(m, hipSetDevice(m->device));
   const size_t capA = (size_t)a->capacity, capB = (size_t)b->capacity, capW = std::min(capA, capB);
   const size_t lds = 32 * (capA + capB) + 16 * capW + 4 * (capB + capA + capB);
-  const bool in_lds = lds <= (size_t)m->lds_limit;
-  const int blocks = std::min(npairs, kMaxBlocks);
   Args g;
   g.a = to_side(a); g.b = to_side(b);
   g.pairs = d_pairs; g.b2a = d_match_b2a; g.a2b = d_match_a2b; g.nm = d_nmatches;
-  g.scratch = nullptr; g.scratch_stride = 0;
-  if (!in_lds) {
-    g.scratch_stride = (((capW * 16 + 15) & ~(size_t)15) + capB * 4 + 255) & ~(size_t)255;
-    if ((rc = grow(m, &m->scratch, g.scratch_stride * blocks)) != ORBX_OK) return rc;
-    g.scratch = m->scratch.p;
-  }
   g.npairs = npairs; g.th = mode == ORBX_MATCH_KEYFRAMES ? 49 : 50; g.kf = mode == ORBX_MATCH_KEYFRAMES; g.check_ori = check_orientation != 0;
   g.wave_node = m->wave_node; g.ratio = nn_ratio;
-  hipStream_t st = stream ? (hipStream_t)stream : m->st;
-  if ((rc = wait_previous(m, st)) != ORBX_OK) return rc;
-  if (in_lds) hipLaunchKernelGGL(k_match_pairs<true>, dim3((unsigned)blocks), dim3(kThreads), lds, st, g);
-  else hipLaunchKernelGGL(k_match_pairs<false>, dim3((unsigned)blocks), dim3(kThreads), 0, st, g);
-  return record_call(m, st);
+  return launch(m, lds <= (size_t)m->lds_limit, lds, (((capW * 16 + 15) & ~(size_t)15) + capB * 4 + 255) & ~(size_t)255, std::min(npairs, kMaxBlocks),
+                kThreads, g, k_match_pairs<true>, k_match_pairs<false>, stream);
 }
 
 int orbx_match_bow_pairs(orbx_match* m, const orbx_match_side* a, const orbx_match_side* b, const int32_t* pairs, int npairs, int mode, float nn_ratio,
@@ -360,28 +332,16 @@ int orbx_match_bow_pairs(orbx_match* m, const orbx_match_side* a, const orbx_mat
   const char* who = "orbx_match_bow_pairs: ";
   int rc = check_call(m, who, a, b, pairs, npairs, mode, match_b2a, match_a2b, nmatches);
   if (rc != ORBX_OK) return rc;
-  const bool same = a == b || std::memcmp(a, b, sizeof(*a)) == 0;   // one batch on both sides is staged once
+  const auto arrays = side_arrays<true, orbx_match_side>({{offsetof(orbx_match_side, d_valid), 0, 1, true}});
   Stager io;
-  struct Off { size_t kps, desc, counts, node, ptr, feat, n, valid; } off[2];
-  const orbx_match_side* sides[2] = {a, b};
-  for (int s = 0; s < (same ? 1 : 2); s++) {
-    const orbx_match_side* h = sides[s];
-    const size_t nf = (size_t)h->nframes, nk = nf * h->capacity;
-    off[s] = {io.in(h->d_kps, nk * sizeof(orbx_keypoint)), io.in(h->d_desc, nk * 32), io.in(h->d_counts, nf * 8), io.in(h->d_fv_node, nk * 4),
-              io.in(h->d_fv_ptr, (nk + nf) * 4), io.in(h->d_fv_feat, nk * 4), io.in(h->d_fv_n, nf * 4), h->d_valid ? io.in(h->d_valid, nk) : 0};
-  }
-  if (same) off[1] = off[0];
+  const StagedSides off = stage_sides(io, a, b, arrays);
   const size_t o_pairs = io.in(pairs, (size_t)npairs * 8);
   const size_t o_b2a = io.out(match_b2a, (size_t)npairs * b->capacity * 4), o_a2b = io.out(match_a2b, (size_t)npairs * a->capacity * 4),
                o_nm = io.out(nmatches, (size_t)npairs * 4);
   if ((rc = upload(m, io)) != ORBX_OK) return rc;
   uint8_t* d = m->io.p;
   orbx_match_side ds[2];
-  for (int s = 0; s < 2; s++) {
-    const Off& o = off[s];
-    ds[s] = {(const orbx_keypoint*)(d + o.kps), d + o.desc, (const int32_t*)(d + o.counts), (const uint32_t*)(d + o.node), (const int32_t*)(d + o.ptr),
-             (const uint32_t*)(d + o.feat), (const int32_t*)(d + o.n), sides[s]->d_valid ? d + o.valid : nullptr, sides[s]->nframes, sides[s]->capacity};
-  }
+  device_sides(d, off, a, b, arrays, ds);
   rc = orbx_match_bow_pairs_device(m, &ds[0], &ds[1], (const int32_t*)(d + o_pairs), npairs, mode, nn_ratio, check_orientation, (int32_t*)(d + o_b2a),
                                    (int32_t*)(d + o_a2b), (int32_t*)(d + o_nm), m->st);
   if (rc != ORBX_OK) return rc;

@@ -1,7 +1,7 @@
 // The host-side core of a side library's handle (liborbx_stereo.so, liborbx_bow.so, liborbx_match.so, liborbx_initmatch.so: DESIGN.md
 // sections 10 and 11).  Host code only; it sits below csrc/, outside kernels_hash().  A handle derives from orbx::side::Handle and adds what
-// is its own.  The device helpers of the pair matchers are in orbx_pair_device.h; what the four chained projection matchers add to this
-// file (their handle, argument checks and plan) is in orbx_window_host.h.
+// is its own.  Each family's host layer is beside this file: the four pair matchers' in orbx_pair_host.h (their device helpers in
+// orbx_pair_device.h), the four chained projection matchers' in orbx_window_host.h, the three projection fronts' in orbx_front_host.h.
 //
 // The rule it keeps: the calls on one handle share its scratch, so each waits for the one before it (wait_previous / record_call around
 // ev_done), and a block of the handle is replaced only once the handle is idle (grow behind quiesce).

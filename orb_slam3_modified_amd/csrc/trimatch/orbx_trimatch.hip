@@ -30,6 +30,7 @@
 
 #include "../side/orbx_handle.h"
 #include "../side/orbx_pair_device.h"
+#include "../side/orbx_pair_host.h"
 #include "../../../include/orbx_trimatch.h"
 
 namespace {
@@ -37,8 +38,6 @@ namespace {
 using namespace orbx::side::dev;
 
 constexpr int kThreads = 512;             // 8 waves
-constexpr int kLdsMax = 152 * 1024;       // dynamic LDS of one workgroup (160 KiB per CU, the static part is below 1 KiB)
-constexpr int kMaxBlocks = 1024;          // workgroups of one launch: each owns one slice of the scratch
 constexpr int kChunk = 16;                // queries of one work item
 constexpr int kThLow = 50;
 constexpr uint32_t kSkip = 0x80000000u, kStereo = 0x40000000u, kIdx = 0x3FFFFFFFu;   // a staged fv_feat entry
@@ -281,21 +280,12 @@ __global__ __launch_bounds__(kThreads) void k_tri_pairs(Args g) {
 
 }  // namespace
 
-struct orbx_trimatch : orbx::side::Handle {   // scratch: per workgroup the global path's work list and staged lists
-  int lds_limit = kLdsMax;                    // ORBX_TRIMATCH_LDS at create
-};
+struct orbx_trimatch : orbx::side::pair::PairHandle {};   // scratch: per workgroup the global path's work list and staged lists
 
 namespace {
 
 using namespace orbx::side;
-
-const char* side_problem(const orbx_trimatch_side* s) {
-  if (!s) return "null side";
-  if (s->nframes < 1 || s->capacity < 1) return "nframes and capacity must be at least 1";
-  if (s->capacity > ORBX_TRIMATCH_MAX_CAPACITY) return "capacity above 65536";
-  if (!s->d_kps || !s->d_desc || !s->d_counts || !s->d_fv_node || !s->d_fv_ptr || !s->d_fv_feat || !s->d_fv_n) return "null buffer in a side";
-  return nullptr;
-}
+using namespace orbx::side::pair;
 
 Side to_side(const orbx_trimatch_side* s) {
   return {(const uint8_t*)s->d_kps, s->d_desc, s->d_counts, s->d_fv_node, s->d_fv_ptr, s->d_fv_feat, s->d_fv_n, s->d_has_point, s->d_uright,
@@ -305,17 +295,14 @@ Side to_side(const orbx_trimatch_side* s) {
 // what both forms check before anything is copied or launched
 int check_call(orbx_trimatch* m, const char* who, const orbx_trimatch_side* a, const orbx_trimatch_side* b, const void* pairs, int npairs,
                const void* geom, const float* scale, const float* sigma2, int nlevels, const void* m12, const void* nm) {
-  for (const orbx_trimatch_side* s : {a, b})
-    if (const char* e = side_problem(s)) return fail(m, ORBX_E_INVALID, std::string(who) + e);
-  if (!pairs || !geom || !m12 || !nm) return fail(m, ORBX_E_INVALID, std::string(who) + "null pairs, geom, matches12 or nmatches");
+  int rc = check_sides<true>(m, who, a, b, ORBX_TRIMATCH_MAX_CAPACITY, "capacity above 65536", pairs && geom && m12 && nm,
+                             "pairs, geom, matches12 or nmatches");
+  if (rc != ORBX_OK) return rc;
   if (!scale || !sigma2) return fail(m, ORBX_E_INVALID, std::string(who) + "null scale_factor or level_sigma2");
   if (nlevels < 1 || nlevels > ORBX_TRIMATCH_MAX_LEVELS)
     return fail(m, ORBX_E_INVALID, std::string(who) + "nlevels = " + std::to_string(nlevels) + " (1 .. 16)");
-  if (npairs < 1) return fail(m, ORBX_E_INVALID, std::string(who) + "npairs = " + std::to_string(npairs) + " (at least 1)");
-  if ((long long)npairs * std::max(a->capacity, 12) > (long long)INT_MAX || (long long)a->nframes * (a->capacity + 1) > (long long)INT_MAX ||
-      (long long)b->nframes * (b->capacity + 1) > (long long)INT_MAX)
-    return fail(m, ORBX_E_INVALID, std::string(who) + "npairs * capacity or nframes * capacity exceeds INT_MAX");
-  return ORBX_OK;
+  if ((rc = check_npairs(m, who, npairs)) != ORBX_OK) return rc;
+  return check_sizes<true>(m, who, a, b, npairs, std::max(a->capacity, 12), "npairs * capacity");
 }
 
 }  // namespace
@@ -324,8 +311,7 @@ extern "C" {
 
 int orbx_trimatch_create(orbx_trimatch** out, int device) {
   return create_handle(out, device, "orbx_trimatch_create", orbx_trimatch_destroy, [](orbx_trimatch* m) {
-    m->lds_limit = env_int("ORBX_TRIMATCH_LDS", 0, kLdsMax, kLdsMax);
-    return allow_lds((const void*)k_tri_pairs<true>, kLdsMax);
+    return open_pair(m, "ORBX_TRIMATCH_LDS", nullptr, (const void*)k_tri_pairs<true>);
   });
 }
 
@@ -347,27 +333,16 @@ int orbx_trimatch_pairs_device(orbx_trimatch* m, const orbx_trimatch_side* a, co
   const size_t capA = (size_t)a->capacity, capB = (size_t)b->capacity;
   const size_t lists = 16 * (size_t)max_work(a->capacity, b->capacity) + 4 * (capA + capB);
   const size_t lds = 32 * (capA + capB) + lists + 4 * capA;
-  const bool in_lds = lds <= (size_t)m->lds_limit;
-  const int blocks = std::min(npairs, kMaxBlocks);
   Args g;
   g.a = to_side(a); g.b = to_side(b);
   g.pairs = d_pairs; g.geom = d_geom; g.m12 = d_matches12; g.nm = d_nmatches;
-  g.scratch = nullptr; g.scratch_stride = 0;
-  if (!in_lds) {
-    g.scratch_stride = (lists + 255) & ~(size_t)255;
-    if ((rc = grow(m, &m->scratch, g.scratch_stride * blocks)) != ORBX_OK) return rc;
-    g.scratch = m->scratch.p;
-  }
   g.npairs = npairs; g.nlevels = nlevels; g.only_stereo = only_stereo != 0; g.coarse = coarse != 0; g.check_ori = check_orientation != 0;
   for (int l = 0; l < ORBX_TRIMATCH_MAX_LEVELS; l++) {
     g.scale[l] = l < nlevels ? scale_factor[l] : 0.0f;
     g.sigma2[l] = l < nlevels ? level_sigma2[l] : 0.0f;
   }
-  hipStream_t st = stream ? (hipStream_t)stream : m->st;
-  if ((rc = wait_previous(m, st)) != ORBX_OK) return rc;
-  if (in_lds) hipLaunchKernelGGL(k_tri_pairs<true>, dim3((unsigned)blocks), dim3(kThreads), lds, st, g);
-  else hipLaunchKernelGGL(k_tri_pairs<false>, dim3((unsigned)blocks), dim3(kThreads), 0, st, g);
-  return record_call(m, st);
+  return launch(m, lds <= (size_t)m->lds_limit, lds, (lists + 255) & ~(size_t)255, std::min(npairs, kMaxBlocks), kThreads, g, k_tri_pairs<true>,
+                k_tri_pairs<false>, stream);
 }
 
 int orbx_trimatch_pairs(orbx_trimatch* m, const orbx_trimatch_side* a, const orbx_trimatch_side* b, const int32_t* pairs, int npairs,
@@ -377,29 +352,16 @@ int orbx_trimatch_pairs(orbx_trimatch* m, const orbx_trimatch_side* a, const orb
   const char* who = "orbx_trimatch_pairs: ";
   int rc = check_call(m, who, a, b, pairs, npairs, geom, scale_factor, level_sigma2, nlevels, matches12, nmatches);
   if (rc != ORBX_OK) return rc;
-  const bool same = a == b || std::memcmp(a, b, sizeof(*a)) == 0;   // one batch on both sides is staged once
+  const auto arrays = side_arrays<true, orbx_trimatch_side>({{offsetof(orbx_trimatch_side, d_has_point), 0, 1, true},
+                                                             {offsetof(orbx_trimatch_side, d_uright), 0, 4, true}});
   Stager io;
-  struct Off { size_t kps, desc, counts, node, ptr, feat, n, has, ur; } off[2];
-  const orbx_trimatch_side* sides[2] = {a, b};
-  for (int s = 0; s < (same ? 1 : 2); s++) {
-    const orbx_trimatch_side* h = sides[s];
-    const size_t nf = (size_t)h->nframes, nk = nf * h->capacity;
-    off[s] = {io.in(h->d_kps, nk * sizeof(orbx_keypoint)), io.in(h->d_desc, nk * 32), io.in(h->d_counts, nf * 8), io.in(h->d_fv_node, nk * 4),
-              io.in(h->d_fv_ptr, (nk + nf) * 4), io.in(h->d_fv_feat, nk * 4), io.in(h->d_fv_n, nf * 4),
-              h->d_has_point ? io.in(h->d_has_point, nk) : 0, h->d_uright ? io.in(h->d_uright, nk * 4) : 0};
-  }
-  if (same) off[1] = off[0];
+  const StagedSides off = stage_sides(io, a, b, arrays);
   const size_t o_pairs = io.in(pairs, (size_t)npairs * 8), o_geom = io.in(geom, (size_t)npairs * 12 * 4);
   const size_t o_12 = io.out(matches12, (size_t)npairs * a->capacity * 4), o_nm = io.out(nmatches, (size_t)npairs * 4);
   if ((rc = upload(m, io)) != ORBX_OK) return rc;
   uint8_t* d = m->io.p;
   orbx_trimatch_side ds[2];
-  for (int s = 0; s < 2; s++) {
-    const Off& o = off[s];
-    ds[s] = {(const orbx_keypoint*)(d + o.kps), d + o.desc, (const int32_t*)(d + o.counts), (const uint32_t*)(d + o.node), (const int32_t*)(d + o.ptr),
-             (const uint32_t*)(d + o.feat), (const int32_t*)(d + o.n), sides[s]->d_has_point ? d + o.has : nullptr,
-             sides[s]->d_uright ? (const float*)(d + o.ur) : nullptr, sides[s]->nframes, sides[s]->capacity};
-  }
+  device_sides(d, off, a, b, arrays, ds);
   rc = orbx_trimatch_pairs_device(m, &ds[0], &ds[1], (const int32_t*)(d + o_pairs), npairs, (const float*)(d + o_geom), scale_factor, level_sigma2,
                                   nlevels, only_stereo, coarse, check_orientation, (int32_t*)(d + o_12), (int32_t*)(d + o_nm), m->st);
   if (rc != ORBX_OK) return rc;

@@ -10,7 +10,8 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._lib import KP_DTYPE, OrbxInitMatchSide, addr, host_array as arr, host_view, ptr
+from ._lib import OrbxInitMatchSide, addr, ptr
+from ._pair import PairResult, PairSide, count, host_call, new_results
 
 LDS_MAX = 152 * 1024     # the largest LDS block of a workgroup (ORBX_INITMATCH_LDS lowers it)
 MAX_CAPACITY = 32768
@@ -27,7 +28,7 @@ def lds_bytes(cap_a: int, cap_b: int) -> int:
 
 
 @dataclass
-class InitSide:
+class InitSide(PairSide):
     """One side of the pairs (orbx_initmatch_side): kps [F, cap] keypoints (28 bytes each), desc [F, cap, 32], counts [F, 2].  Torch tensors
     or raw HBM addresses for pairs_device, numpy arrays for pairs."""
     kps: object
@@ -35,20 +36,11 @@ class InitSide:
     counts: object
     nframes: int
     capacity: int
-
-    def _struct(self) -> OrbxInitMatchSide:
-        return OrbxInitMatchSide(*(addr(t) or None for t in (self.kps, self.desc, self.counts)), int(self.nframes), int(self.capacity))
-
-    def _host(self) -> "InitSide":
-        """Contiguous numpy arrays of the ABI's element types."""
-        F, cap = int(self.nframes), int(self.capacity)
-        kps = np.ascontiguousarray(self.kps)
-        assert kps.nbytes == F * cap * KP_DTYPE.itemsize
-        return InitSide(kps, arr(self.desc, np.uint8, F, cap, 32), arr(self.counts, np.int32, F, 2), F, cap)
+    _STRUCT, _FIELDS = OrbxInitMatchSide, ("kps", "desc", "counts")
 
 
 @dataclass
-class InitResult:
+class InitResult(PairResult):
     """nmatches [P] (the reference's return value, -1 for a malformed pair), matches12 [P, a.capacity], matches21 [P, b.capacity] or None
     (-1: no match), prev_xy [P, a.capacity, 2] or None (vbPrevMatched, updated); torch tensors from pairs_device, numpy arrays from pairs.
     result[p] = (nmatches, matches12 row, matches21 row) of pair p on the host."""
@@ -56,12 +48,7 @@ class InitResult:
     matches12: object
     matches21: object
     prev_xy: object = None
-
-    def __len__(self) -> int:
-        return int(self.nmatches.shape[0])
-
-    def __getitem__(self, p: int):
-        return int(host_view(self.nmatches[p:p + 1])[0]), *(None if t is None else host_view(t[p]) for t in (self.matches12, self.matches21))
+    _ROWS = ("matches12", "matches21")
 
 
 class InitMatchBatch(_lib.SideHandle):
@@ -77,12 +64,9 @@ class InitMatchBatch(_lib.SideHandle):
         """orbx_initmatch_pairs_device: `pairs` [P, 2] int32 (frame of a, frame of b) on the device, `bounds` (mnMinX, mnMinY, mnMaxX, mnMaxY)
         of b's frames, `prev_xy` [P, a.capacity, 2] float32 on the device (updated in place) or None; asynchronous on `stream` (None or 0: the
         handle's own).  Without `out` the result tensors are allocated on the pairs' device (torch)."""
-        P = int(pairs.shape[0]) if npairs is None else int(npairs)
+        P = count(pairs, npairs)
         if out is None:
-            import torch
-            dev = pairs.device if hasattr(pairs, "device") else torch.device("cuda", self.device_id)
-            out = InitResult(torch.empty(P, dtype=torch.int32, device=dev), torch.empty((P, a.capacity), dtype=torch.int32, device=dev),
-                             torch.empty((P, b.capacity), dtype=torch.int32, device=dev))
+            out = InitResult(*new_results(P, ((), (a.capacity,), (b.capacity,)), self, pairs))
         out.prev_xy = prev_xy
         sa, sb = a._struct(), b._struct()
         bd = (C.c_float * 4)(*[float(v) for v in bounds])
@@ -96,12 +80,9 @@ class InitMatchBatch(_lib.SideHandle):
               prev_xy=None) -> InitResult:
         """orbx_initmatch_pairs on numpy arrays of the same layout; returns when the results are on the host.  `prev_xy` [P, a.capacity, 2]
         float32 is copied: the updated rows are the result's prev_xy."""
-        ha = a._host()
-        hb = ha if b is a else b._host()
-        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
-        P = len(pairs)
+        ha, hb, pairs, P = host_call(a, b, pairs)
         prev = None if prev_xy is None else np.array(prev_xy, np.float32, order="C").reshape(P, ha.capacity, 2)
-        out = InitResult(np.zeros(P, np.int32), np.zeros((P, ha.capacity), np.int32), np.zeros((P, hb.capacity), np.int32), prev)
+        out = InitResult(*new_results(P, ((), (ha.capacity,), (hb.capacity,))), prev)
         sa, sb = ha._struct(), hb._struct()
         bd = (C.c_float * 4)(*[float(v) for v in bounds])
         self._check(self._M.orbx_initmatch_pairs(self._h, C.byref(sa), C.byref(sb), ptr(pairs), P, bd, int(window_size), float(nn_ratio),

@@ -7,16 +7,15 @@ import ctypes as C
 from dataclasses import dataclass
 from typing import Optional
 
-import numpy as np
-
 from . import _lib
-from ._lib import KP_DTYPE, OrbxMatchSide, addr, host_array as arr, host_view, ptr
+from ._lib import OrbxMatchSide, addr, ptr
+from ._pair import FV, PairResult, PairSide, count, host_call, new_results
 
 FRAME, KEYFRAMES = 0, 1   # ORBX_MATCH_FRAME, ORBX_MATCH_KEYFRAMES
 
 
 @dataclass
-class MatchSide:
+class MatchSide(PairSide):
     """One side of the pairs (orbx_match_side): kps [F, cap] keypoints (28 bytes each), desc [F, cap, 32], counts [F, 2], the four
     FeatureVector arrays as BowDeviceResult holds them, valid [F, cap] uint8 or None.  Torch tensors or raw HBM addresses for
     bow_pairs_device, numpy arrays for bow_pairs."""
@@ -30,39 +29,22 @@ class MatchSide:
     nframes: int
     capacity: int
     valid: object = None
+    _STRUCT, _FIELDS = OrbxMatchSide, ("kps", "desc", "counts") + FV + ("valid",)
 
     @classmethod
     def of(cls, kps, desc, counts, fv, nframes: int, capacity: int, valid=None) -> "MatchSide":
         """From a batch extraction's buffers and a BowDeviceResult (or anything with fv_node / fv_ptr / fv_feat / fv_n)."""
         return cls(kps, desc, counts, fv.fv_node, fv.fv_ptr, fv.fv_feat, fv.fv_n, int(nframes), int(capacity), valid)
 
-    def _struct(self) -> OrbxMatchSide:
-        return OrbxMatchSide(*(addr(t) or None for t in (self.kps, self.desc, self.counts, self.fv_node, self.fv_ptr, self.fv_feat, self.fv_n,
-                                                           self.valid)), int(self.nframes), int(self.capacity))
-
-    def _host(self) -> "MatchSide":
-        """Contiguous numpy arrays of the ABI's element types."""
-        F, cap = int(self.nframes), int(self.capacity)
-        kps = np.ascontiguousarray(self.kps)
-        assert kps.nbytes == F * cap * KP_DTYPE.itemsize
-        return MatchSide(kps, arr(self.desc, np.uint8, F, cap, 32), arr(self.counts, np.int32, F, 2), arr(self.fv_node, np.uint32, F, cap),
-                         arr(self.fv_ptr, np.int32, F, cap + 1), arr(self.fv_feat, np.uint32, F, cap), arr(self.fv_n, np.int32, F), F, cap,
-                         None if self.valid is None else arr(self.valid, np.uint8, F, cap))
-
 
 @dataclass
-class MatchResult:
+class MatchResult(PairResult):
     """nmatches [P] (the reference's return value, -1 for a malformed pair), b2a [P, b.capacity], a2b [P, a.capacity] (-1: no match); torch
     tensors from bow_pairs_device, numpy arrays from bow_pairs.  result[p] = (nmatches, b2a row, a2b row) of pair p on the host."""
     nmatches: object
     b2a: object
     a2b: object
-
-    def __len__(self) -> int:
-        return int(self.nmatches.shape[0])
-
-    def __getitem__(self, p: int):
-        return int(host_view(self.nmatches[p:p + 1])[0]), *(None if t is None else host_view(t[p]) for t in (self.b2a, self.a2b))
+    _ROWS = ("b2a", "a2b")
 
 
 class MatchBatch(_lib.SideHandle):
@@ -77,12 +59,9 @@ class MatchBatch(_lib.SideHandle):
                          stream=None, out: Optional[MatchResult] = None, npairs: Optional[int] = None) -> MatchResult:
         """orbx_match_bow_pairs_device: `pairs` [P, 2] int32 (frame of a, frame of b) on the device; asynchronous on `stream` (None or 0: the
         handle's own).  Without `out` the result tensors are allocated on the pairs' device (torch)."""
-        P = int(pairs.shape[0]) if npairs is None else int(npairs)
+        P = count(pairs, npairs)
         if out is None:
-            import torch
-            dev = pairs.device if hasattr(pairs, "device") else torch.device("cuda", self.device_id)
-            out = MatchResult(torch.empty(P, dtype=torch.int32, device=dev), torch.empty((P, b.capacity), dtype=torch.int32, device=dev),
-                              torch.empty((P, a.capacity), dtype=torch.int32, device=dev))
+            out = MatchResult(*new_results(P, ((), (b.capacity,), (a.capacity,)), self, pairs))
         sa, sb = a._struct(), b._struct()
         self._check(self._M.orbx_match_bow_pairs_device(self._h, C.byref(sa), C.byref(sb), ptr(addr(pairs)), P, int(mode), float(nn_ratio),
                                                         int(bool(check_orientation)), ptr(addr(out.b2a)), ptr(addr(out.a2b)),
@@ -91,11 +70,8 @@ class MatchBatch(_lib.SideHandle):
 
     def bow_pairs(self, a: MatchSide, b: MatchSide, pairs, mode: int = FRAME, nn_ratio: float = 0.7, check_orientation: bool = True) -> MatchResult:
         """orbx_match_bow_pairs on numpy arrays of the same layout; returns when the results are on the host."""
-        ha = a._host()
-        hb = ha if b is a else b._host()
-        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
-        P = len(pairs)
-        out = MatchResult(np.zeros(P, np.int32), np.zeros((P, hb.capacity), np.int32), np.zeros((P, ha.capacity), np.int32))
+        ha, hb, pairs, P = host_call(a, b, pairs)
+        out = MatchResult(*new_results(P, ((), (hb.capacity,), (ha.capacity,))))
         sa, sb = ha._struct(), hb._struct()
         self._check(self._M.orbx_match_bow_pairs(self._h, C.byref(sa), C.byref(sb), ptr(pairs), P, int(mode), float(nn_ratio),
                                                  int(bool(check_orientation)), ptr(out.b2a), ptr(out.a2b), ptr(out.nmatches)))

@@ -9,10 +9,9 @@ import ctypes as C
 from dataclasses import dataclass
 from typing import Optional
 
-import numpy as np
-
 from . import _lib
-from ._lib import KP_DTYPE, OrbxRigBowRig, OrbxRigBowSide, addr, host_array as arr, host_view, ptr
+from ._lib import KP_DTYPE, OrbxRigBowRig, OrbxRigBowSide, addr, ptr
+from ._pair import FV, PairResult, PairSide, count, host_call, new_results
 
 FRAME, KEYFRAMES = 0, 1   # ORBX_RIGBOW_FRAME, ORBX_RIGBOW_KEYFRAMES
 LDS_MAX = 152 * 1024
@@ -36,7 +35,7 @@ class StackedFrames:
 
 
 @dataclass
-class RigBowSide:
+class RigBowSide(PairSide):
     """One side of the pairs (orbx_rigbow_side): MatchSide's fields on stacked frames and nleft [F] int32 (Nleft; -1 or None: single-camera
     frames).  Torch tensors or raw HBM addresses for bow_pairs_device, numpy arrays for bow_pairs."""
     kps: object
@@ -50,6 +49,7 @@ class RigBowSide:
     capacity: int
     valid: object = None
     nleft: object = None
+    _STRUCT, _FIELDS = OrbxRigBowSide, ("kps", "desc", "counts") + FV + ("valid", "nleft")
 
     @classmethod
     def of(cls, stacked: StackedFrames, fv, valid=None) -> "RigBowSide":
@@ -57,35 +57,16 @@ class RigBowSide:
         return cls(stacked.kps, stacked.desc, stacked.counts, fv.fv_node, fv.fv_ptr, fv.fv_feat, fv.fv_n, int(stacked.nframes),
                    int(stacked.capacity), valid, stacked.nleft)
 
-    def _struct(self) -> OrbxRigBowSide:
-        return OrbxRigBowSide(*(addr(t) or None for t in (self.kps, self.desc, self.counts, self.fv_node, self.fv_ptr, self.fv_feat, self.fv_n,
-                                                            self.valid, self.nleft)), int(self.nframes), int(self.capacity))
-
-    def _host(self) -> "RigBowSide":
-        """Contiguous numpy arrays of the ABI's element types."""
-        F, cap = int(self.nframes), int(self.capacity)
-        kps = np.ascontiguousarray(self.kps)
-        assert kps.nbytes == F * cap * KP_DTYPE.itemsize
-        return RigBowSide(kps, arr(self.desc, np.uint8, F, cap, 32), arr(self.counts, np.int32, F, 2), arr(self.fv_node, np.uint32, F, cap),
-                          arr(self.fv_ptr, np.int32, F, cap + 1), arr(self.fv_feat, np.uint32, F, cap), arr(self.fv_n, np.int32, F), F, cap,
-                          None if self.valid is None else arr(self.valid, np.uint8, F, cap),
-                          None if self.nleft is None else arr(self.nleft, np.int32, F))
-
 
 @dataclass
-class RigBowResult:
+class RigBowResult(PairResult):
     """nmatches [P] (the reference's return value, -1 for a malformed pair), b2a [P, b.capacity] (the A feature left in each B slot), a2b
     [P, a.capacity, 2] ({left B slot, right B slot} of each A feature); -1: none.  Torch tensors from bow_pairs_device, numpy arrays from
     bow_pairs.  result[p] = (nmatches, b2a row, a2b rows) of pair p on the host."""
     nmatches: object
     b2a: object
     a2b: object
-
-    def __len__(self) -> int:
-        return int(self.nmatches.shape[0])
-
-    def __getitem__(self, p: int):
-        return int(host_view(self.nmatches[p:p + 1])[0]), *(None if t is None else host_view(t[p]) for t in (self.b2a, self.a2b))
+    _ROWS = ("b2a", "a2b")
 
 
 class RigBowBatch(_lib.SideHandle):
@@ -123,12 +104,9 @@ class RigBowBatch(_lib.SideHandle):
                          stream=None, out: Optional[RigBowResult] = None, npairs: Optional[int] = None) -> RigBowResult:
         """orbx_rigbow_pairs_device: `pairs` [P, 2] int32 (frame of a, frame of b) on the device; asynchronous on `stream` (None or 0: the
         handle's own).  Without `out` the result tensors are allocated on the pairs' device (torch)."""
-        P = int(pairs.shape[0]) if npairs is None else int(npairs)
+        P = count(pairs, npairs)
         if out is None:
-            import torch
-            dev = pairs.device if hasattr(pairs, "device") else torch.device("cuda", self.device_id)
-            out = RigBowResult(torch.empty(P, dtype=torch.int32, device=dev), torch.empty((P, b.capacity), dtype=torch.int32, device=dev),
-                               torch.empty((P, a.capacity, 2), dtype=torch.int32, device=dev))
+            out = RigBowResult(*new_results(P, ((), (b.capacity,), (a.capacity, 2)), self, pairs))
         sa, sb = a._struct(), b._struct()
         self._check(self._M.orbx_rigbow_pairs_device(self._h, C.byref(sa), C.byref(sb), ptr(addr(pairs)), P, int(mode), float(nn_ratio),
                                                      int(bool(check_orientation)), ptr(addr(out.b2a)), ptr(addr(out.a2b)),
@@ -137,11 +115,8 @@ class RigBowBatch(_lib.SideHandle):
 
     def bow_pairs(self, a: RigBowSide, b: RigBowSide, pairs, mode: int = FRAME, nn_ratio: float = 0.7, check_orientation: bool = True) -> RigBowResult:
         """orbx_rigbow_pairs on numpy arrays of the same layout; returns when the results are on the host."""
-        ha = a._host()
-        hb = ha if b is a else b._host()
-        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
-        P = len(pairs)
-        out = RigBowResult(np.zeros(P, np.int32), np.zeros((P, hb.capacity), np.int32), np.zeros((P, ha.capacity, 2), np.int32))
+        ha, hb, pairs, P = host_call(a, b, pairs)
+        out = RigBowResult(*new_results(P, ((), (hb.capacity,), (ha.capacity, 2))))
         sa, sb = ha._struct(), hb._struct()
         self._check(self._M.orbx_rigbow_pairs(self._h, C.byref(sa), C.byref(sb), ptr(pairs), P, int(mode), float(nn_ratio),
                                               int(bool(check_orientation)), ptr(out.b2a), ptr(out.a2b), ptr(out.nmatches)))

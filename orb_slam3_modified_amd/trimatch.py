@@ -11,7 +11,8 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._lib import KP_DTYPE, OrbxTriMatchSide, addr, host_array as arr, host_view, ptr
+from ._lib import OrbxTriMatchSide, addr, ptr
+from ._pair import FV, PairResult, PairSide, count, host_call, new_results
 
 LDS_MAX = 152 * 1024     # the largest LDS block of a workgroup (ORBX_TRIMATCH_LDS lowers it)
 MAX_CAPACITY = 65536
@@ -44,7 +45,7 @@ def geometry(F12, ep) -> np.ndarray:
 
 
 @dataclass
-class TriMatchSide:
+class TriMatchSide(PairSide):
     """One side of the pairs (orbx_trimatch_side): kps [F, cap] keypoints (28 bytes each), desc [F, cap, 32], counts [F, 2], the four
     FeatureVector arrays as BowDeviceResult holds them, has_point [F, cap] uint8 or None (no feature has a MapPoint), uright [F, cap] float32
     or None (monocular).  Torch tensors or raw HBM addresses for pairs_device, numpy arrays for pairs."""
@@ -59,39 +60,21 @@ class TriMatchSide:
     capacity: int
     has_point: object = None
     uright: object = None
+    _STRUCT, _FIELDS = OrbxTriMatchSide, ("kps", "desc", "counts") + FV + ("has_point", "uright")
 
     @classmethod
     def of(cls, kps, desc, counts, fv, nframes: int, capacity: int, has_point=None, uright=None) -> "TriMatchSide":
         """From a batch extraction's buffers and a BowDeviceResult (or anything with fv_node / fv_ptr / fv_feat / fv_n)."""
         return cls(kps, desc, counts, fv.fv_node, fv.fv_ptr, fv.fv_feat, fv.fv_n, int(nframes), int(capacity), has_point, uright)
 
-    def _struct(self) -> OrbxTriMatchSide:
-        return OrbxTriMatchSide(*(addr(t) or None for t in (self.kps, self.desc, self.counts, self.fv_node, self.fv_ptr, self.fv_feat, self.fv_n,
-                                                              self.has_point, self.uright)), int(self.nframes), int(self.capacity))
-
-    def _host(self) -> "TriMatchSide":
-        """Contiguous numpy arrays of the ABI's element types."""
-        F, cap = int(self.nframes), int(self.capacity)
-        kps = np.ascontiguousarray(self.kps)
-        assert kps.nbytes == F * cap * KP_DTYPE.itemsize
-        return TriMatchSide(kps, arr(self.desc, np.uint8, F, cap, 32), arr(self.counts, np.int32, F, 2), arr(self.fv_node, np.uint32, F, cap),
-                            arr(self.fv_ptr, np.int32, F, cap + 1), arr(self.fv_feat, np.uint32, F, cap), arr(self.fv_n, np.int32, F), F, cap,
-                            None if self.has_point is None else arr(self.has_point, np.uint8, F, cap),
-                            None if self.uright is None else arr(self.uright, np.float32, F, cap))
-
 
 @dataclass
-class TriMatchResult:
+class TriMatchResult(PairResult):
     """nmatches [P] (the reference's return value, -1 for a malformed pair), matches12 [P, a.capacity] (vMatches12; -1: no match); torch
     tensors from pairs_device, numpy arrays from pairs.  result[p] = (nmatches, matches12 row) of pair p on the host."""
     nmatches: object
     matches12: object
-
-    def __len__(self) -> int:
-        return int(self.nmatches.shape[0])
-
-    def __getitem__(self, p: int):
-        return int(host_view(self.nmatches[p:p + 1])[0]), host_view(self.matches12[p])
+    _ROWS = ("matches12",)
 
     def matched_pairs(self, p: int) -> list:
         """vMatchedPairs of pair p: (index in A, index in B), ascending in the A index."""
@@ -121,11 +104,9 @@ class TriMatchBatch(_lib.SideHandle):
         """orbx_trimatch_pairs_device: `pairs` [P, 2] int32 (keyframe of a, keyframe of b) and `geom` [P, 12] float32 on the device,
         `scale_factor` / `level_sigma2` host arrays of b's extractor; asynchronous on `stream` (None or 0: the handle's own).  Without `out`
         the result tensors are allocated on the pairs' device (torch)."""
-        P = int(pairs.shape[0]) if npairs is None else int(npairs)
+        P = count(pairs, npairs)
         if out is None:
-            import torch
-            dev = pairs.device if hasattr(pairs, "device") else torch.device("cuda", self.device_id)
-            out = TriMatchResult(torch.empty(P, dtype=torch.int32, device=dev), torch.empty((P, a.capacity), dtype=torch.int32, device=dev))
+            out = TriMatchResult(*new_results(P, ((), (a.capacity,)), self, pairs))
         sa, sb = a._struct(), b._struct()
         _s, _q, ps, pq, nl = _tables(scale_factor, level_sigma2)
         self._check(self._M.orbx_trimatch_pairs_device(self._h, C.byref(sa), C.byref(sb), ptr(addr(pairs)), P, ptr(addr(geom)), ps, pq, nl,
@@ -136,12 +117,9 @@ class TriMatchBatch(_lib.SideHandle):
     def pairs(self, a: TriMatchSide, b: TriMatchSide, pairs, geom, scale_factor, level_sigma2, only_stereo: bool = False, coarse: bool = False,
               check_orientation: bool = True) -> TriMatchResult:
         """orbx_trimatch_pairs on numpy arrays of the same layout; returns when the results are on the host."""
-        ha = a._host()
-        hb = ha if b is a else b._host()
-        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
-        P = len(pairs)
+        ha, hb, pairs, P = host_call(a, b, pairs)
         geom = np.ascontiguousarray(geom, np.float32).reshape(P, 12)
-        out = TriMatchResult(np.zeros(P, np.int32), np.zeros((P, ha.capacity), np.int32))
+        out = TriMatchResult(*new_results(P, ((), (ha.capacity,))))
         sa, sb = ha._struct(), hb._struct()
         _s, _q, ps, pq, nl = _tables(scale_factor, level_sigma2)
         self._check(self._M.orbx_trimatch_pairs(self._h, C.byref(sa), C.byref(sb), ptr(pairs), P, ptr(geom), ps, pq, nl, int(bool(only_stereo)),
