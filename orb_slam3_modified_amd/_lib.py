@@ -34,6 +34,7 @@ PROJECT_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_project.so")
 SIM3_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_sim3.so")               # LoopClosing's Sim3 projections and agreement pass (include/orbx_sim3.h)
 RIGMATCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_rigmatch.so")       # the two-camera rig blocks of the two Tracking matchers (include/orbx_rigmatch.h)
 RIGBOW_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_rigbow.so")           # the rig block of SearchByBoW and the stacked rig frame (include/orbx_rigbow.h)
+MPGEOM_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "liborbx_mpgeom.so")           # the batched MapPoint::UpdateNormalAndDepth (include/orbx_mpgeom.h)
 
 ORBX_OK, ORBX_E_INVALID, ORBX_E_EMPTY, ORBX_E_DEVICE, ORBX_E_CAPACITY, ORBX_E_FORMAT = 0, -1, -2, -3, -4, -5
 NUM_KERNELS = 6
@@ -658,10 +659,34 @@ def rigbow_lib(path: str = RIGBOW_LIB_PATH) -> C.CDLL:
     return M
 
 
+class OrbxMpgeomSide(C.Structure):
+    """orbx_mpgeom_side (include/orbx_mpgeom.h)."""
+    _fields_ = [("d_kps", C.c_void_p), ("d_counts", C.c_void_p), ("d_nleft", C.c_void_p), ("d_centres", C.c_void_p), ("nframes", C.c_int),
+                ("capacity", C.c_int)]
+
+
+def mpgeom_lib(path: str = MPGEOM_LIB_PATH) -> C.CDLL:
+    """liborbx_mpgeom.so.  `_orbx_mpgeom_symbols`: every name of include/orbx_mpgeom.h, bound here with its signature.  `path`: a timing
+    build of the same source."""
+    vp, i32, sp = C.c_void_p, C.c_int, C.POINTER(OrbxMpgeomSide)
+    call = [sp, vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, i32, i32, vp, vp]   # side .. min_dist
+    sig = {
+        "orbx_mpgeom_create": (i32, [C.POINTER(vp), i32]),
+        "orbx_mpgeom_destroy": (None, [vp]),
+        "orbx_mpgeom_last_error": (C.c_char_p, [vp]),
+        "orbx_mpgeom_update_device": (i32, [vp] + call + [vp]),
+        "orbx_mpgeom_update": (i32, [vp] + call),
+        "orbx_mpgeom_update_reference": (i32, call),
+    }
+    M = _load_side(path, sig)
+    M._orbx_mpgeom_symbols = tuple(sig)
+    return M
+
+
 class SideHandle:
     """A handle of a side library whose entry points are <prefix>_create / _destroy / _last_error (StereoBatch, BowBatch, MatchBatch,
     InitMatchBatch, TriMatchBatch, FuseBatch, DistinctBatch, ScoreBatch, FisheyeBatch, LocalMatchBatch, LastMatchBatch, ProjMatchBatch,
-    PlaceBatch, PlaceIndex, FrustumBatch, ProjectBatch, Sim3Batch, RigMatchBatch, RigBowBatch)."""
+    PlaceBatch, PlaceIndex, FrustumBatch, ProjectBatch, Sim3Batch, RigMatchBatch, RigBowBatch, NormalDepthBatch)."""
 
     def __init__(self, library: C.CDLL, prefix: str, *create_args):
         self._L, self._prefix, self._h = library, prefix, C.c_void_p(0)

@@ -30,6 +30,8 @@ LIBS is the one place that knows them, one record per library; what is stale, wh
                         (include/orbx_rigmatch.h)
   liborbx_rigbow.so     the two-camera rig block of SearchByBoW, batched, and the stacked rig frame it runs on (include/orbx_rigbow.h);
                         takes nothing from the product
+  liborbx_mpgeom.so     the batched MapPoint::UpdateNormalAndDepth, written in place into the projection fronts' table of map points
+                        (include/orbx_mpgeom.h); takes nothing from the product
 The libraries beside the product link liborbx.so and use its ABI (and orbx_internal.h where they read a context's buffers).  Their sources sit
 in subdirectories of csrc/, outside kernels_hash(): the committed counter files measure the product's kernels, which they do not change.
 A new one is one more record ("Adding a side library")."""
@@ -88,6 +90,8 @@ RIGMATCH_OUT = os.path.join(os.path.dirname(OUT), "liborbx_rigmatch.so")
 RIGMATCH_SOURCE = os.path.join("rigmatch", "orbx_rigmatch.hip")
 RIGBOW_OUT = os.path.join(os.path.dirname(OUT), "liborbx_rigbow.so")
 RIGBOW_SOURCE = os.path.join("rigbow", "orbx_rigbow.hip")
+MPGEOM_OUT = os.path.join(os.path.dirname(OUT), "liborbx_mpgeom.so")
+MPGEOM_SOURCE = os.path.join("mpgeom", "orbx_mpgeom.hip")
 FRONT_CORE = (os.path.join("side", "orbx_front_device.h"), os.path.join("side", "orbx_front_host.h"))   # what the three projection fronts share
 PAIR_CORE = (os.path.join("side", "orbx_pair_device.h"), os.path.join("side", "orbx_pair_host.h"))   # what the four pair matchers share
 
@@ -121,11 +125,12 @@ LIBS = (Lib(OUT, tuple(SOURCES)),
         Lib(PROJECT_OUT, (PROJECT_SOURCE,), hidden=True, deps=FRONT_CORE),
         Lib(SIM3_OUT, (SIM3_SOURCE,), hidden=True, deps=FRONT_CORE),
         Lib(RIGMATCH_OUT, (RIGMATCH_SOURCE,), hidden=True, deps=WINDOW_CORE),
-        Lib(RIGBOW_OUT, (RIGBOW_SOURCE,), hidden=True, deps=PAIR_CORE))
+        Lib(RIGBOW_OUT, (RIGBOW_SOURCE,), hidden=True, deps=PAIR_CORE),
+        Lib(MPGEOM_OUT, (MPGEOM_SOURCE,), hidden=True, deps=(os.path.join("side", "orbx_handle.h"), os.path.join("side", "orbx_front_device.h"))))
 HEADERS = ("orbx.h", "orbx_debug.h", "orbx_train.h", "orbx_stereo.h", "orbx_bow.h", "orbx_match.h", "orbx_initmatch.h", "orbx_trimatch.h",
            "orbx_fuse.h", "orbx_mpdesc.h", "orbx_score.h", "orbx_fisheye.h", "orbx_localmatch.h", "orbx_lastmatch.h",
            "orbx_projmatch.h", "orbx_place.h", "orbx_placeindex.h", "orbx_frustum.h", "orbx_project.h", "orbx_sim3.h", "orbx_rigmatch.h",
-           "orbx_rigbow.h")
+           "orbx_rigbow.h", "orbx_mpgeom.h")
 # -ffp-contract=off: the float paths (fastAtan2 polynomial, BRIEF rotation) must not be fused into FMAs,
 # the CPU reference evaluates them as separate IEEE operations (DESIGN.md "bit-exactness").
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall",
